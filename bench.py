@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end images/sec at 512x512 (BASELINE.json's metric) on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step`, the status word of the
+last batch's records).  Everything else it can measure or check runs with --full only: the independent re-computation of
+the last batch (`verify`), the per-kernel timings and rooflines (`kernel_ms`, `roofline`, `roofline_forward`,
+`conv_layers`) and the CPU baseline (`cpu_baseline`).  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32, the status words float64: the batch's records and a seeded sample of its network output); the
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script LAUNCHES ITS OWN RANKS (one process per GPU through
 `python -m torch.distributed.run`, rendezvous on 127.0.0.1) before anything touches the GPU, waits for them and exits with
@@ -54,6 +61,10 @@ FLOP_PER_IMAGE = 2 * FLOP_PER_FORWARD_EXECUTED                          # flip: 
 UP2_FLOP_PER_FORWARD = 4 * 2 * 9 * (128 * 128 * 256 * 256 + 64 * 64 * 384 * 384 + 32 * 32 * 512 * 512 + 16 * 16 * 640 * 640)
 UP2_FLOP_SAVED_PER_FORWARD = UP2_FLOP_PER_FORWARD * 5 / 9
 ST_DEFINED, ST_SORT_UNDEFINED = 0x7F, 8                                 # include/posepaf.h:53-61
+# The kernel choice per layer shape of the default geometry (128 images per step), tuned by this script's warm-up on an MI355X
+# for the libposepaf.so whose hash it names; a library of other bytes ignores it and the warm-up tunes (about 25 s).  Remade by
+# `POSEPAF_CACHE_DIR=DIR python bench.py --retune` and keeping the batch-128 entries of DIR/conv_choice_<hash>.json.
+BENCH_CHOICE_TABLE = os.path.join(ROOT, "profiles", "conv_choice_b128.json")
 
 
 def parse(argv=None):
@@ -74,7 +85,16 @@ def parse(argv=None):
     ap.add_argument("--no-verify", action="store_true", help="skip the independent re-computation of the last batch")
     ap.add_argument("--multiscale", action="store_true",
                     help="BASELINE configs[4]: original path, scale search {0.5, 1.0, 1.5} x 512 + flip, float64 accumulation")
+    ap.add_argument("--full", action="store_true",
+                    help="also re-compute the last batch independently, time the kernels one by one (rooflines) and run the "
+                         "CPU baseline; a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (records, a sample of the network output)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
     if a.batch <= 0:
         a.batch = 32 if a.multiscale else 128
     return a
@@ -107,6 +127,44 @@ def build_scenes(batch, dtype=None):
     dtype = dtype or np.float16
     uniq = [synth.make_net_output(p, 9000 + i, dtype=dtype) for i, p in enumerate(SCENE_PEOPLE)]
     return np.stack([uniq[i % len(uniq)] for i in range(batch)]), uniq
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_IMAGES = 512   # records of at most this many images (a seeded sample of larger batches): 20 MB of float32
+DUMP_MAP_IMAGES = 4     # network output of this many images of the last batch (seeded sample): 26 MB of float32
+
+
+def sample_images(n, k):
+    """sorted indices of k of n images, the same in every run (all of them when n <= k)"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(2024).choice(n, k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, recs, maps=None):
+    """recs: pp_record array of the last timed step (every rank's, in rank order); maps: (image indices, float32 maps) or None.
+    Writes float32 arrays: the record fields per image, the person slots past n_humans zeroed (they hold no result)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    idx = sample_images(len(recs), DUMP_MAX_IMAGES)
+    recs = recs[idx]
+    out = {"records_image_index": idx}
+    for f in ("n_humans", "n_peaks", "status", "n_connections"):
+        out[f"records_{f}"] = recs[f]
+    valid = np.arange(recs["humans"].shape[1])[None, :] < recs["n_humans"][:, None]
+    for f in ("peak_id", "x", "y", "part_score", "score", "n_parts"):
+        v = recs["humans"][f]
+        out[f"records_humans_{f}"] = np.where(valid.reshape(valid.shape + (1,) * (v.ndim - 2)), v, 0)
+    if maps is not None:
+        out["maps_image_index"], out["maps"] = maps
+    total = 0
+    for name, v in out.items():   # ids, coordinates and counts are exact in float32; a status word needs float64
+        v = np.ascontiguousarray(v, dtype=np.float64 if name == "records_status" else np.float32)
+        np.save(os.path.join(path, f"{name}.npy"), v)
+        total += v.nbytes
+    assert total <= 64 << 20, total
+    return sorted(out)
 
 
 _W_ORC, _W_SCENES = None, None
@@ -255,6 +313,9 @@ class StubEngine:
     def oracle_sample(self, rec, n=8):
         return None
 
+    def maps_sample(self):
+        return None
+
     def extras(self, a, dt, world):
         return {"stub": True, "steps_run": self.steps_run}
 
@@ -289,9 +350,10 @@ class GpuEngine:
         if say:   # the warm-up times every layer shape once: say so on stderr, one line per shape
             fused_model.set_progress(say)
             say(f"building the model; warm-up tunes each convolution shape at batch {a.batch} unless the choice table "
-                f"{fused_model.default_table_path()} exists (under a minute)")
+                f"{fused_model.default_table_path()} or {os.path.relpath(BENCH_CHOICE_TABLE, ROOT)} holds it (under a minute)")
         self.model = None if a.postproc_only else build_inference_model(dev, fused=not a.plain_model)
-        self.table_loaded = fused_model.load_table() if not a.retune else 0
+        # (the cache's own table first: where both hold a shape, its entry is kept)
+        self.table_loaded = (fused_model.load_table(), fused_model.load_table(BENCH_CHOICE_TABLE)) if not a.retune else (0, 0)
         self.eng = InferenceEngine(self.model, self.post, B, local, rules="cpp", use_graph=not (a.no_graph or a.multiscale),
                                    inject_scale=1e-3, max_image_hw=(IMG, IMG), n_slots=2, postproc_only=a.postproc_only,
                                    progress=say)
@@ -485,6 +547,18 @@ class GpuEngine:
         n = min(n, p.b)
         return p.maps[:n].cpu().numpy(), records_to_numpy(rec)[:n]
 
+    def maps_sample(self):
+        """(image indices, float32 network output of those images) of the last batch -- the maps the post-processing read,
+        after the synthetic scenes were added; None on the multi-scale line, which keeps no maps"""
+        import numpy as np
+        p = getattr(self, "plan", None)
+        if p is None or p.maps is None or self.a.multiscale:
+            return None
+        self.sync()
+        idx = sample_images(p.b, DUMP_MAP_IMAGES)
+        sel = self.torch.from_numpy(idx).to(p.maps.device)
+        return idx, p.maps.index_select(0, sel).float().cpu().numpy().astype(np.float32)
+
     def extras(self, a, dt, world):
         """roofline of the hand-written kernels (HIP events on the launch stream) + forward roofline"""
         B = a.batch
@@ -547,8 +621,9 @@ class GpuEngine:
                                       "pooled_or_channel_sum_outputs_fused": sum(1 for v in side.values() if v),
                                       "shapes_streaming_1x1_kernel": sum(1 for v in ch.values() if v == 105),
                                       "choice_table_hash": fused_model.table_hash(),
-                                      "choice_table": "loaded from " + fused_model.default_table_path() if self.table_loaded
-                                      else "tuned in this run's warm-up"}
+                                      "choice_table": f"{self.table_loaded[0]} entries loaded from {fused_model.default_table_path()}, "
+                                                      f"{self.table_loaded[1]} from {os.path.relpath(BENCH_CHOICE_TABLE, ROOT)}, "
+                                                      "the other shapes tuned in this run's warm-up"}
         return out
 
 
@@ -619,16 +694,21 @@ def main(argv=None):
         dt = float(t.item())
 
     # every rank checks its own records; the verdicts are combined so that rank 0's line and every exit code agree
-    recs = records_to_numpy(rec)
+    recs = allrec = records_to_numpy(rec)
     status_or = int(np.bitwise_or.reduce(recs["status"].astype(np.uint32)))
     humans = int(recs["n_humans"].sum())
     if world > 1:
         allrec = gathered.cpu().numpy().view(recs.dtype)
         status_or = int(np.bitwise_or.reduce(allrec["status"].astype(np.uint32)))
         humans = int(allrec["n_humans"].sum())
+    if a.dump_outputs and rank == 0:   # before anything else runs on the engine: the last timed step's results, as they are
+        dump_outputs(a.dump_outputs, allrec, eng.maps_sample())
     allowed = ST_SORT_UNDEFINED | (32 if a.multiscale else 0)
     bad_status = bool(status_or & ~ST_DEFINED) or bool(status_or & ~allowed)
-    verdict = {"ok": True, "skipped": "--no-verify"} if a.no_verify else eng.verify(rec)
+    if not a.full:
+        verdict = {"ok": True, "skipped": "plain run (--full re-computes the last batch)"}
+    else:
+        verdict = {"ok": True, "skipped": "--no-verify"} if a.no_verify else eng.verify(rec)
     if world > 1:   # every rank re-computes its own last batch; one failing rank fails the job
         t = torch.tensor([0 if verdict["ok"] else 1], dtype=torch.int32, device=gdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -656,8 +736,9 @@ def main(argv=None):
                        "parallelism": f"image-sharded x{world}"},
             "humans_found_in_batch": humans, "status_or": status_or, "verify": verdict,
         }
-        out.update(eng.extras(a, dt, world))
-        if not a.no_cpu_baseline and world == 1 and not stub:   # reported on rank 0 at N = 1 only
+        if a.full:
+            out.update(eng.extras(a, dt, world))
+        if a.full and not a.no_cpu_baseline and world == 1 and not stub:   # reported on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(a.cpu_seconds, a.cpu_cores, check=eng.oracle_sample(rec))
             if out["cpu_baseline"].get("records_vs_oracle") == "DIFFERENT":
                 verdict["ok"] = False

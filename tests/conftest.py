@@ -22,13 +22,47 @@ def oracle():
     return Oracle()
 
 
+def reference_key(joint_list, paf_hwc, min_img_size) -> str:
+    """identifies one process_paf call by its inputs (as the compiled reference receives them)"""
+    import hashlib
+
+    import numpy as np
+    h = hashlib.sha256()
+    for a in (joint_list, paf_hwc):
+        a = np.ascontiguousarray(a, np.float32)
+        h.update(repr(a.shape).encode())
+        h.update(a.tobytes())
+    h.update(str(int(min_img_size)).encode())
+    return h.hexdigest()[:24]
+
+
+class StoredReference:
+    """The reference's own C++ process_paf as recorded by tests/golden/make_reference_cpp.py (golden G6): the result of a
+    call is looked up by its inputs.  Where the compiled reference is present (oracle/_ref, built from the reference's
+    sources by oracle/Makefile) every call also runs it, and it must reproduce the record."""
+
+    def __init__(self):
+        import numpy as np
+        from oracle.oracle import REF_SO, Reference
+        self.store = np.load(os.path.join(GOLDEN, "g6_reference_process_paf.npz"))
+        self.live = Reference() if os.path.exists(REF_SO) else None
+
+    def process_paf(self, joint_list, paf_hwc, min_img_size):
+        import numpy as np
+        key = reference_key(joint_list, paf_hwc, min_img_size)
+        assert f"{key}_ids" in self.store.files, \
+            "no recorded reference result for these inputs: add the case to tests/golden/make_reference_cpp.py and re-run it"
+        want = {f: self.store[f"{key}_{f}"] for f in ("ids", "scores", "peaks")}
+        if self.live is not None:
+            got = self.live.process_paf(joint_list, paf_hwc, min_img_size)
+            assert all(np.array_equal(got[f], want[f]) for f in want), "the compiled reference no longer gives the recorded result"
+        return want
+
+
 @pytest.fixture(scope="session")
 def reference_cpp():
-    """The reference's own C++ pafprocess, compiled into oracle/_ref (prebuilt file on the GPU box)."""
-    from oracle.oracle import REF_SO, Reference
-    if not os.path.exists(REF_SO) and not os.path.isdir("/root/reference"):
-        pytest.skip("oracle/_ref not built and no reference tree")
-    return Reference()
+    """The reference's own C++ pafprocess: its recorded results, checked against oracle/_ref where that is built."""
+    return StoredReference()
 
 
 def load_scene(key):
