@@ -34,7 +34,7 @@ extern "C" int pp_conv_ld_f16(const void *x, const void *w, const void *bias, co
     if (al & 15) return PP_ERR_BAD_ARG;
     const long ho = (long)h + 2L * pad - (long)dilation * (ksize - 1), wo = (long)wd + 2L * pad - (long)dilation * (ksize - 1);
     if (ho <= 0 || wo <= 0) return PP_ERR_BAD_ARG;
-    // 32-bit byte offsets inside the kernels: each tensor at most 2 GB
+    // 32-bit byte offsets inside the kernels: each tensor at most 2 GB (one of exactly 2 GB runs as sub-batches, posepaf_conv_inst.hip)
     if ((long)n * h * wd * ldx * 2 > (1L << 31) || (long)n * ho * wo * ldy * 2 > (1L << 31)) return PP_ERR_TOO_LARGE;
     const PPConvArgs a{x, w, bias, extra, y, n, h, wd, c_in, c_out, ksize, ksize, pad, dilation, ldx, ldy, extra_mode, slope, stream};
     int rc = -1;

@@ -169,11 +169,15 @@ int run_part(const PPConvArgs &a, int n0, int n, bool launch) {
 }
 
 // The device templates bound some 32-bit GEMM extents (e.g. M * K * 2 bytes <= 2 GB in the pipelined variants); a batch that
-// exceeds them is run as 2, 4 or 8 equal sub-batches (images are independent rows of the implicit GEMM).
+// exceeds them is run as 2, 4 or 8 equal sub-batches (images are independent rows of the implicit GEMM).  The templates accept
+// a tensor of exactly 2^31 bytes but do not compute it right (the bench's 256 x 256 x 256 x 64 1x1 convolution: wrong values in
+// the first pixels of image 0), so a sub-batch's input and output stay below 2^31 bytes.
 int run(const PPConvArgs &a) {
+    const long ho = a.H + 2L * a.pad - (long)a.dil * (a.R - 1), wo = a.W + 2L * a.pad - (long)a.dil * (a.S - 1);
     for (int parts = 1; parts <= 8; parts *= 2) {
         if (a.N % parts) break;
         const int n = a.N / parts;
+        if ((long)n * a.H * a.W * a.ldx * 2 >= (1L << 31) || n * ho * wo * a.ldy * 2 >= (1L << 31)) continue;
         if (run_part(a, 0, n, false) != 0) continue;
         for (int p = 0; p < parts; p++)
             if (run_part(a, p * n, n, true) != 0) return -1;

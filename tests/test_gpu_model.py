@@ -1045,9 +1045,11 @@ def test_own_convolution_kernels_are_deterministic_under_load():
     """Race detector.  The hand-written kernels keep LDS-DMA in flight across barriers and count it by hand (vmcnt); a wrong count
     shows only when the memory system is loaded -- the four-tap halo instances read a halo that was still arriving at 256
     samples while every small-shape test passed.  Every kernel family at the bench geometry, 256 samples, launched repeatedly
-    on the same operands: all results BIT-identical, and the first right against torch on a slice."""
+    on the same operands: all results BIT-identical, and the first right against torch on a slice and over the WHOLE batch (fp32
+    reference in chunks of images: a wrong result that repeats, e.g. a wrong tile or image offset past the first images, fails)."""
     import ctypes as C
     import torch.nn.functional as F
+    import conv_reference as cr
     from posepaf import _lib, fused_model as fm
     L = _lib.load()
     vp = C.c_void_p
@@ -1055,7 +1057,18 @@ def test_own_convolution_kernels_are_deterministic_under_load():
     g = torch.Generator(device="cpu").manual_seed(97)
     n, reps = 256, 6
 
-    def repeat(launch, shape_out, check):
+    def whole_batch(ref_chunk, tol, label, nb=16):
+        """-> check(y): every image of y against ref_chunk(i0, i1) (fp32, TF32 off), |err| <= tol * max(1, max |ref|)"""
+        with cr.NoTF32(), torch.no_grad():
+            refs = [ref_chunk(i0, min(n, i0 + nb)) for i0 in range(0, n, nb)]
+        bound = tol * max(1.0, max(float(r.abs().max()) for r in refs))
+
+        def check(y):
+            for j, r in enumerate(refs):
+                cr.assert_close(y[j * nb:j * nb + len(r)], r, bound, label, img0=j * nb)
+        return check
+
+    def repeat(launch, shape_out, check, whole):
         first = None
         for r in range(reps):
             y = torch.full(shape_out, float("nan"), dtype=torch.float16, device="cuda").contiguous(memory_format=torch.channels_last)
@@ -1065,6 +1078,7 @@ def test_own_convolution_kernels_are_deterministic_under_load():
                 first = y
                 assert torch.isfinite(y).all()
                 check(y)
+                whole(y)
             else:
                 assert torch.equal(y, first), ("repeat differs", r, float((y.float() - first.float()).abs().max()))
 
@@ -1080,11 +1094,14 @@ def test_own_convolution_kernels_are_deterministic_under_load():
         w4 = f._collapsed_weights()
         ref = F.leaky_relu(F.conv2d(F.interpolate(x[:2].float(), scale_factor=2, mode="nearest"), f.weight.float(), f.bias.float(), 1, 1),
                            0.01) + e1[:2].float()
+        whole = whole_batch(lambda i0, i1: F.leaky_relu(F.conv2d(F.interpolate(x[i0:i1].float(), scale_factor=2, mode="nearest"),
+                                                                 f.weight.float(), f.bias.float(), 1, 1), 0.01) + e1[i0:i1].float(),
+                            4e-3, f"collapsed {ci}x{h}x{w}")
         for bn in (512, 128):
             repeat(lambda y: L.pp_conv_up2_collapsed_f16(vp(x.data_ptr()), vp(w4.data_ptr()), vp(f.bias.data_ptr()), vp(e1.data_ptr()), None,
                                                          vp(y.data_ptr()), n, h, w, ci, co, 2, 0.01, bn, st),
                    (n, co, 2 * h, 2 * w), lambda y: (y[:2].float() - ref).abs().max().item() <= 4e-3 * ref.abs().max().item() or
-                   pytest.fail("collapsed convolution wrong"))
+                   pytest.fail("collapsed convolution wrong"), whole)
         del x, e1
     # nine-tap halo kernel (128- and 64-wide tiles), dilated instances, implicit GEMM, streaming 1x1
     for ci, co, h, w, k, d in ((128, 128, 128, 128, 3, 1), (192, 192, 64, 64, 3, 1), (128, 128, 128, 128, 3, 4), (256, 128, 64, 64, 1, 1)):
@@ -1093,15 +1110,17 @@ def test_own_convolution_kernels_are_deterministic_under_load():
         b = torch.randn(co, generator=g).cuda().half()
         pad = d if k == 3 else 0
         ref = F.leaky_relu(F.conv2d(x[:2].float(), wt.float(), b.float(), 1, pad, d), 0.01)
+        whole = whole_batch(lambda i0, i1: F.leaky_relu(F.conv2d(x[i0:i1].float(), wt.float(), b.float(), 1, pad, d), 0.01), 2e-3,
+                            f"{k}x{k} {ci}->{co} {h}x{w} dilation {d}")
 
         def check(y):
             assert (y[:2].float() - ref).abs().max().item() <= 2e-3 * max(1.0, ref.abs().max().item())
         for bn in ((512, 128 if co % 128 == 0 else 64) if k == 3 else (128,)):
             repeat(lambda y: L.pp_conv_own_f16(vp(x.data_ptr()), vp(wt.data_ptr()), vp(b.data_ptr()), None, vp(y.data_ptr()), n, h, w, ci, co,
-                                               k, pad, d, 0, 0.01, bn, st), (n, co, h, w), check)
+                                               k, pad, d, 0, 0.01, bn, st), (n, co, h, w), check, whole)
         if k == 1:
             repeat(lambda y: L.pp_pw_f16(vp(x.data_ptr()), None, vp(wt.data_ptr()), vp(b.data_ptr()), None, None, vp(y.data_ptr()), None,
-                                         n * h * w, h * w, ci, co, co, 0, 0.01, st), (n, co, h, w), check)
+                                         n * h * w, h * w, ci, co, co, 0, 0.01, st), (n, co, h, w), check, whole)
         del x
 
 
