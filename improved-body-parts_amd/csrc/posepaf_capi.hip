@@ -509,6 +509,64 @@ int pp_original_accumulate_all(pp_ctx *ctx, int batch, int n_scales, const void 
     return PP_OK;
 }
 
+// ---- the rotation search (utils/parse_skeletons.py:214-218, :265-267)
+int pp_warp_affine_f32(const float *src, float *dst, long n, int h, int w, int channels, int hwc, const double *m_inv,
+                       void *stream) {
+    if (!src || !dst || !m_inv || src == dst || n <= 0 || h <= 0 || w <= 0 || (hwc && channels <= 0)) return PP_ERR_BAD_ARG;
+    return pp::launch_warp_affine_f32(src, dst, n, h, w, hwc ? channels : 1, hwc ? 1 : 0, m_inv, static_cast<hipStream_t>(stream)) ==
+                   hipSuccess
+               ? PP_OK
+               : PP_ERR_HIP;
+}
+
+int pp_original_accumulate_affine(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip, int pad_down,
+                                  int pad_right, int img_h, int img_w, int n_div, const double *m_inv, float *scratch_planar,
+                                  float *scratch_up, float *scratch_warp, double *heat_acc, double *paf_acc, void *stream) {
+    if (!m_inv)
+        return pp_original_accumulate(ctx, batch, net_out_dev, dtype, h, w, flip, pad_down, pad_right, img_h, img_w, n_div,
+                                      scratch_planar, scratch_up, heat_acc, paf_acc, stream);
+    if (!ctx || !net_out_dev || !scratch_planar || !scratch_up || !scratch_warp || !heat_acc || !paf_acc || batch <= 0 || h <= 0 ||
+        w <= 0 || img_h <= 0 || img_w <= 0 || n_div <= 0 || pad_down < 0 || pad_right < 0 || pad_down >= 4 * h ||
+        pad_right >= 4 * w || (dtype != PP_F16 && dtype != PP_F32))
+        return PP_ERR_BAD_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int uh = 4 * h, uw = 4 * w, ch = uh - pad_down, cw = uw - pad_right;
+    PP_HIP(ctx, pp::launch_flip_average_planar(net_out_dev, dtype, batch, h, w, flip, scratch_planar, st));
+    PP_HIP(ctx, pp::launch_resize_cubic(scratch_planar, (long)h * w, w, h, w, scratch_up, 0, batch * PP_NUM_CH, uh, uw, 0.25, 0.25,
+                                        1.0f, st));
+    // warpAffine(M_rev) of the whole x4 map, before the crop (:265-267)
+    PP_HIP(ctx, pp::launch_warp_affine_f32(scratch_up, scratch_warp, (long)batch * PP_NUM_CH, uh, uw, 1, 0, m_inv, st));
+    const double sx = 1.0 / ((double)img_w / (double)cw), sy = 1.0 / ((double)img_h / (double)ch);
+    for (int b = 0; b < batch; b++) {
+        const float *up_b = scratch_warp + (size_t)b * PP_NUM_CH * uh * uw;
+        PP_HIP(ctx, pp::launch_resize_cubic(up_b, (long)uh * uw, uw, ch, cw, paf_acc + (size_t)b * PP_NUM_LIMB * img_h * img_w, 1,
+                                            PP_NUM_LIMB, img_h, img_w, sx, sy, (float)n_div, st));
+        PP_HIP(ctx, pp::launch_resize_cubic(up_b + (size_t)PP_NUM_LIMB * uh * uw, (long)uh * uw, uw, ch, cw,
+                                            heat_acc + (size_t)b * PP_NUM_HEAT * img_h * img_w, 1, PP_NUM_HEAT, img_h, img_w, sx,
+                                            sy, (float)n_div, st));
+    }
+    return PP_OK;
+}
+
+int pp_original_accumulate_all_affine(pp_ctx *ctx, int batch, int n_entries, const void *const *net_out_dev, int dtype, const int *h,
+                                      const int *w, int flip, const int *pad_down, const int *pad_right,
+                                      const double *const *m_inv, int img_h, int img_w, double *heat_acc, double *paf_acc,
+                                      void *stream) {
+    if (!ctx || !net_out_dev || !h || !w || !pad_down || !pad_right || !heat_acc || !paf_acc || batch <= 0 || img_h <= 0 ||
+        img_w <= 0 || n_entries <= 0 || (dtype != PP_F16 && dtype != PP_F32))
+        return PP_ERR_BAD_ARG;
+    if (n_entries > 6) return PP_ERR_UNSUPPORTED;
+    for (int i = 0; i < n_entries; i++)
+        if (!net_out_dev[i] || h[i] <= 0 || w[i] <= 0 || pad_down[i] < 0 || pad_right[i] < 0 || pad_down[i] >= 4 * h[i] ||
+            pad_right[i] >= 4 * w[i])
+            return PP_ERR_BAD_ARG;
+    const hipError_t e = pp::launch_accumulate_scales_affine(n_entries, net_out_dev, dtype, batch, h, w, flip, pad_down, pad_right,
+                                                             m_inv, img_h, img_w, heat_acc, paf_acc, static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return PP_ERR_UNSUPPORTED;   // an entry whose tiles do not fit LDS: use the per-entry chain
+    PP_HIP(ctx, e);
+    return PP_OK;
+}
+
 int pp_original_finish(pp_ctx *ctx, int batch, int img_h, int img_w, float thre1, const double *heat_acc, const double *paf_acc,
                        unsigned char *mask_scratch, void *peaks64_scratch, pp_record *records_dev, void *stream) {
     if (!ctx || !heat_acc || !paf_acc || !mask_scratch || !peaks64_scratch || batch <= 0 || batch > ctx->max_batch ||

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/posepaf.h"
+#include "posepaf_affine.h"
 
 namespace {
 
@@ -505,6 +506,86 @@ extern "C" int pp_preprocess_u8(const void *images_u8, void *out, int dtype, int
     else
         hipLaunchKernelGGL(k_preprocess<float>, grid, block, 0, st, static_cast<const unsigned char *>(images_u8),
                            static_cast<float *>(out), batch, h, w, Hp, Wp, flip, pad_norm);
+    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
+}
+
+// The same with the test-time rotation (utils/parse_skeletons.py:212-221): the padded float image of each input (never
+// materialised: u8 / 255 inside the image, pad_value / 255 in the padding) is warped with cv2.warpAffine(M, (0, 0)) -- m_inv
+// is M inverted on the host (posepaf/rotation.py), sampling as posepaf_affine.h -- and the W-mirror written is that of the
+// WARPED image.  The warp reads 0 outside the padded frame, so a rotated input has black corners, not pad grey.
+namespace {
+struct PadImage {
+    const unsigned char *img;
+    int H, W, Hp, Wp;
+    float pad_norm;
+    __device__ __forceinline__ void get(long b, int y, int x, float v[3]) const {
+        if (y < 0 || x < 0 || y >= Hp || x >= Wp) {
+            v[0] = v[1] = v[2] = 0.0f;
+        } else if (y < H && x < W) {
+            const unsigned char *p = img + ((b * H + y) * W + x) * 3;
+            v[0] = (float)p[0] / 255.0f;
+            v[1] = (float)p[1] / 255.0f;
+            v[2] = (float)p[2] / 255.0f;
+        } else {
+            v[0] = v[1] = v[2] = pad_norm;
+        }
+    }
+};
+
+template <typename OutT>
+__global__ __launch_bounds__(256) void k_preprocess_affine(const PadImage I, OutT *__restrict__ out, int B, int flip,
+                                                           const pp::Affine6 M) {
+    const long npix = (long)B * I.Hp * I.Wp;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const int ns = flip ? 2 : 1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
+        const int x = (int)(i % I.Wp);
+        long t = i / I.Wp;
+        const int y = (int)(t % I.Hp);
+        const long b = t / I.Hp;
+        const pp::AffineTap tp = pp::affine_tap(M.m, x, y);
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        if (!pp::affine_outside(tp, I.Hp, I.Wp)) {
+            float a[3], c[3], d[3], e[3];
+            I.get(b, tp.sy, tp.sx, a);
+            I.get(b, tp.sy, tp.sx + 1, c);
+            I.get(b, tp.sy + 1, tp.sx, d);
+            I.get(b, tp.sy + 1, tp.sx + 1, e);
+#pragma unroll
+            for (int k = 0; k < 3; k++) v[k] = pp::affine_combine(tp, a[k], c[k], d[k], e[k]);
+        }
+        OutT *o0 = out + (((b * ns) * I.Hp + y) * I.Wp + x) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; c++) o0[c] = cvt_out<OutT>(v[c]);
+        if (flip) {
+            OutT *o1 = out + (((b * ns + 1) * I.Hp + y) * I.Wp + (I.Wp - 1 - x)) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; c++) o1[c] = cvt_out<OutT>(v[c]);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int pp_preprocess_u8_affine(const void *images_u8, void *out, int dtype, int batch, int h, int w, int pad_to,
+                                       int pad_value, int flip, const double *m_inv, void *stream) {
+    if (!images_u8 || !out || !m_inv || batch <= 0 || h <= 0 || w <= 0 || pad_to <= 0 || (dtype != PP_F16 && dtype != PP_F32))
+        return PP_ERR_BAD_ARG;
+    PadImage I;
+    I.img = static_cast<const unsigned char *>(images_u8);
+    I.H = h;
+    I.W = w;
+    I.Hp = (h + pad_to - 1) / pad_to * pad_to;
+    I.Wp = (w + pad_to - 1) / pad_to * pad_to;
+    I.pad_norm = (float)pad_value / 255.0f;
+    pp::Affine6 M;
+    for (int k = 0; k < 6; k++) M.m[k] = m_inv[k];
+    const long npix = (long)batch * I.Hp * I.Wp;
+    const dim3 grid(grid_for(npix)), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == PP_F16)
+        hipLaunchKernelGGL(k_preprocess_affine<__half>, grid, block, 0, st, I, static_cast<__half *>(out), batch, flip, M);
+    else
+        hipLaunchKernelGGL(k_preprocess_affine<float>, grid, block, 0, st, I, static_cast<float *>(out), batch, flip, M);
     return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
 }
 

@@ -25,9 +25,12 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdlib>
 
 #include "posepaf_internal.h"
+#include "posepaf_affine.h"
 
 namespace pp {
 
@@ -3225,7 +3228,161 @@ struct AccParams {
     float n_div;
     double *heat_acc, *paf_acc;
 };
+// The rotation search (utils/parse_skeletons.py:265-267): an entry may carry the inverted matrix of cv2.warpAffine(M_rev), which
+// warps the FULL x4 map (4h x 4w, padding included, 0 outside it) before the crop.  Only the warped instance
+// (k_accumulate_scales_affine) takes these; k_accumulate_scales keeps AccParams and the code it had.
+struct AccScaleWarp : AccScale {
+    int warp;              // 0: this entry is not rotated (the plain steps above)
+    double m[6];           // inverted matrix (posepaf/rotation.py, posepaf_affine.h)
+    float fwd[6];          // its inverse (the forward matrix), only to skip U elements no warp tap reads
+};
+struct AccParamsWarp {
+    AccScaleWarp s[kAccMaxScales];
+    int n, flip, img_h, img_w, u_cap, a_cap;   // u_cap: U tile or pre-image box, a_cap: A tile
+    float n_div;
+    double *heat_acc, *paf_acc;
+    int w_cap;                                 // warped-and-cropped region the resize taps reach
+    int r_cap;                                 // rows of that region (its row terms precede the column terms in LDS)
+};
 __device__ __forceinline__ int src_floor(int d, double scale) { return (int)floorf((float)(((double)d + 0.5) * scale - 0.5)); }
+
+// cv2.resize(INTER_CUBIC) value at output (dy, dx) of a staged region (rows r0.., columns c0.., row length m) of a map whose
+// taps clamp to (ch, cw) -- the same expressions as k_resize_cubic
+__device__ __forceinline__ float resize_tap_lds(const float *src, int r0, int c0, int m, int ch, int cw, double scale_x,
+                                                double scale_y, int dy, int dx) {
+    float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
+    const int sx = (int)floorf(fx);
+    fx = __fadd_rn(fx, -(float)sx);
+    float fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    fy = __fadd_rn(fy, -(float)sy);
+    float ca[4], cb[4];
+    cubic_coeffs(fx, ca);
+    cubic_coeffs(fy, cb);
+    const int x0 = clampi(sx - 1, 0, cw - 1) - c0, x1 = clampi(sx, 0, cw - 1) - c0, x2 = clampi(sx + 1, 0, cw - 1) - c0,
+              x3 = clampi(sx + 2, 0, cw - 1) - c0;
+    float hrow[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const float *row = src + (clampi(sy - 1 + r, 0, ch - 1) - r0) * m;
+        float hv = __fmul_rn(row[x0], ca[0]);
+        hv = __fadd_rn(hv, __fmul_rn(row[x1], ca[1]));
+        hv = __fadd_rn(hv, __fmul_rn(row[x2], ca[2]));
+        hv = __fadd_rn(hv, __fmul_rn(row[x3], ca[3]));
+        hrow[r] = hv;
+    }
+    float v = __fmul_rn(hrow[0], cb[0]);
+    v = __fadd_rn(v, __fmul_rn(hrow[1], cb[1]));
+    v = __fadd_rn(v, __fmul_rn(hrow[2], cb[2]));
+    return __fadd_rn(v, __fmul_rn(hrow[3], cb[3]));
+}
+
+// flip-average of rows [ar0, ar0 + an) x columns [ac0, ac0 + am) of one channel into sA (the A tile)
+template <typename T>
+__device__ __forceinline__ void stage_flip_average(const void *net, int b, int c, int cf, int ns, int flip, int h, int w, int ar0,
+                                                   int an, int ac0, int am, float *sA) {
+    const long plane = (long)h * w;
+    const T *o0 = static_cast<const T *>(net) + (((long)b * ns) * PP_NUM_CH + c) * plane;
+    const T *o1 = static_cast<const T *>(net) + (((long)b * ns + 1) * PP_NUM_CH + cf) * plane;
+    for (int i = threadIdx.x; i < an * am; i += 256) {
+        const int y = ar0 + i / am, x = ac0 + i % am;
+        float v;
+        if (sizeof(T) == 2) {
+            const __half *p0 = reinterpret_cast<const __half *>(o0), *p1 = reinterpret_cast<const __half *>(o1);
+            v = flip ? __half2float(__hmul(__hadd(p0[y * w + x], p1[y * w + (w - 1 - x)]), __float2half(0.5f)))
+                     : __half2float(p0[y * w + x]);
+        } else {
+            const float *p0 = reinterpret_cast<const float *>(o0), *p1 = reinterpret_cast<const float *>(o1);
+            v = flip ? __fadd_rn(p0[y * w + x], p1[y * w + (w - 1 - x)]) / 2.0f : p0[y * w + x];
+        }
+        sA[i] = v;
+    }
+}
+
+// One rotated entry of the warped instance: per tile three regions are staged -- A (network output, flip-averaged), the
+// bounding box of the warp's pre-image on the FULL x4 map U (+1 for the bilinear taps), and the warped-and-cropped region W the
+// resize taps reach.  Resize taps clamp to the CROPPED size (ch, cw); warp taps address the whole 4h x 4w map (the pad rows /
+// columns the crop drops included) and read 0 outside it.  Same expressions as the chain (k_flip_average_planar,
+// k_resize_cubic, k_warp_affine_f32), so the accumulators are bit-identical to it.
+template <typename T>
+__device__ __forceinline__ void accumulate_warped_entry(const AccScaleWarp &S, const AccParamsWarp &P, int b, int c, int cf, int ns,
+                                                        int oy0, int oy1, int ox0, int ox1, int lx, int ly, float *sU, float *sA,
+                                                        float *sW, double acc[4]) {
+    const int uh = 4 * S.h, uw = 4 * S.w;
+    int wr0, wr1, wc0, wc1;
+    if (S.identity) {
+        wr0 = oy0, wr1 = oy1 - 1, wc0 = ox0, wc1 = ox1 - 1;
+    } else {
+        wr0 = clampi(src_floor(oy0, S.sy) - 1, 0, S.ch - 1), wr1 = clampi(src_floor(oy1 - 1, S.sy) + 2, 0, S.ch - 1);
+        wc0 = clampi(src_floor(ox0, S.sx) - 1, 0, S.cw - 1), wc1 = clampi(src_floor(ox1 - 1, S.sx) + 2, 0, S.cw - 1);
+    }
+    const int rn = wr1 - wr0 + 1, rm = wc1 - wc0 + 1;
+    // ---- OpenCV's row / column terms of the fixed-point source coordinates, once per row and column of W
+    int2 *tRow = reinterpret_cast<int2 *>(sW + P.w_cap), *tCol = tRow + P.r_cap;
+    for (int i = threadIdx.x; i < rn + rm; i += 256) {
+        if (i < rn) tRow[i] = affine_row(S.m, wr0 + i);
+        else tCol[i - rn] = affine_col(S.m, wc0 + i - rn);
+    }
+    // ---- box of U the warp taps reach: the source coordinates are affine up to the fixed-point rounding (< 1/32 px), so
+    // those of W's corners bound every pixel's to within one pixel; +1 more for the bilinear tap
+    int y0 = 0x7fffffff, y1 = -0x7fffffff, x0 = 0x7fffffff, x1 = -0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        int sx, sy, fx, fy;
+        affine_src(S.m, (k & 1) ? wc1 : wc0, (k & 2) ? wr1 : wr0, sx, sy, fx, fy);
+        y0 = min(y0, sy), y1 = max(y1, sy), x0 = min(x0, sx), x1 = max(x1, sx);
+    }
+    const int br0 = max(y0 - 1, 0), br1 = min(y1 + 2, uh - 1), bc0 = max(x0 - 1, 0), bc1 = min(x1 + 2, uw - 1);
+    int bn = br1 - br0 + 1, bm = bc1 - bc0 + 1;
+    if (bn <= 0 || bm <= 0) bn = bm = 0;
+    if (bn * bm > P.u_cap) bn = P.u_cap / bm;   // never taken (the host bound has slack); keeps LDS in range regardless
+    if (bn > 0) {
+        const int ar0 = clampi(src_floor(br0, 0.25) - 1, 0, S.h - 1), ar1 = clampi(src_floor(br1, 0.25) + 2, 0, S.h - 1);
+        const int ac0 = clampi(src_floor(bc0, 0.25) - 1, 0, S.w - 1), ac1 = clampi(src_floor(bc1, 0.25) + 2, 0, S.w - 1);
+        const int an = min(ar1 - ar0 + 1, P.a_cap / (ac1 - ac0 + 1)), am = ac1 - ac0 + 1;
+        stage_flip_average<T>(S.net, b, c, cf, ns, P.flip, S.h, S.w, ar0, an, ac0, am, sA);
+        __syncthreads();
+        // ---- U over the box: x4 bicubic of A, taps clamped to the map.  The box of a rotated region is up to twice its
+        // area: an element whose image under the forward matrix lies more than 3 px outside W is read by no warp tap
+        // (a tap is within 1.5 px of its pixel's source) and is skipped
+        const float wy0 = (float)wr0 - 3.0f, wy1 = (float)wr1 + 3.0f, wx0 = (float)wc0 - 3.0f, wx1 = (float)wc1 + 3.0f;
+        for (int i = threadIdx.x; i < bn * bm; i += 256) {
+            const int uy = br0 + i / bm, ux = bc0 + i % bm;
+            const float fx = S.fwd[0] * (float)ux + S.fwd[1] * (float)uy + S.fwd[2];
+            const float fy = S.fwd[3] * (float)ux + S.fwd[4] * (float)uy + S.fwd[5];
+            if (fx < wx0 || fx > wx1 || fy < wy0 || fy > wy1) continue;
+            sU[i] = resize_tap_lds(sA, ar0, ac0, am, S.h, S.w, 0.25, 0.25, uy, ux);
+        }
+    }
+    __syncthreads();
+    // ---- W: cv2.warpAffine(U, M_rev, (0, 0)) over the region the resize taps reach
+    for (int i = threadIdx.x; i < rn * rm; i += 256) {
+        const AffineTap t = affine_tap_rc(tRow[i / rm], tCol[i % rm]);
+        float v = 0.0f;
+        if (!affine_outside(t, uh, uw)) {
+            float q[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int ty = t.sy + (k >> 1), tx = t.sx + (k & 1);
+                const bool in = ty >= 0 && ty < uh && tx >= 0 && tx < uw && ty - br0 < bn;
+                q[k] = in ? sU[(ty - br0) * bm + (tx - bc0)] : 0.0f;
+            }
+            v = affine_combine(t, q[0], q[1], q[2], q[3]);
+        }
+        sW[i] = v;
+    }
+    __syncthreads();
+    // ---- resize to the image size (:276-277), += value / n in float64 (:280-281)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int dy = oy0 + ly + 8 * k, dx = ox0 + lx;
+        if (dy < oy1 && dx < ox1) {
+            const float v = S.identity ? sW[(dy - wr0) * rm + (dx - wc0)]
+                                       : resize_tap_lds(sW, wr0, wc0, rm, S.ch, S.cw, S.sx, S.sy, dy, dx);
+            acc[k] = __dadd_rn(acc[k], (double)(v / P.n_div));
+        }
+    }
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_accumulate_scales(const AccParams P) {
@@ -3350,6 +3507,98 @@ __global__ __launch_bounds__(256) void k_accumulate_scales(const AccParams P) {
     for (int k = 0; k < 4; k++) {
         const int dy = oy0 + ly + 8 * k, dx = ox0 + lx;
         if (dy < oy1 && dx < ox1) D[(long)dy * P.img_w + dx] = acc[k];
+    }
+}
+
+// The same with rotated entries (pp_original_accumulate_all_affine); LDS: U tile / pre-image box, A tile, W region.  Entries
+// without a matrix take the steps of k_accumulate_scales (through the shared helpers: same expressions, same order).
+template <typename T>
+__global__ __launch_bounds__(256) void k_accumulate_scales_affine(const AccParamsWarp P) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    float *sU = reinterpret_cast<float *>(lds_raw);
+    float *sA = sU + P.u_cap;
+    float *sW = sA + P.a_cap;
+    const int tiles_x = (P.img_w + kAccTile - 1) / kAccTile;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int c = blockIdx.y, b = blockIdx.z;
+    const int oy0 = ty * kAccTile, ox0 = tx * kAccTile;
+    const int oy1 = min(oy0 + kAccTile, P.img_h), ox1 = min(ox0 + kAccTile, P.img_w);
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+    const int ns = P.flip ? 2 : 1;
+    const int cf = c < PP_NUM_LIMB ? d_flip_paf_ord[c] : PP_NUM_LIMB + d_flip_heat_ord[c - PP_NUM_LIMB];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int si = 0; si < P.n; si++) {
+        const AccScaleWarp &S = P.s[si];
+        if (S.warp) {
+            accumulate_warped_entry<T>(S, P, b, c, cf, ns, oy0, oy1, ox0, ox1, lx, ly, sU, sA, sW, acc);
+        } else {
+            int ur0, ur1, uc0, uc1;
+            if (S.identity) {
+                ur0 = oy0, ur1 = oy1 - 1, uc0 = ox0, uc1 = ox1 - 1;
+            } else {
+                ur0 = clampi(src_floor(oy0, S.sy) - 1, 0, S.ch - 1), ur1 = clampi(src_floor(oy1 - 1, S.sy) + 2, 0, S.ch - 1);
+                uc0 = clampi(src_floor(ox0, S.sx) - 1, 0, S.cw - 1), uc1 = clampi(src_floor(ox1 - 1, S.sx) + 2, 0, S.cw - 1);
+            }
+            const int un = ur1 - ur0 + 1, um = uc1 - uc0 + 1;
+            const int ar0 = clampi(src_floor(ur0, 0.25) - 1, 0, S.h - 1), ar1 = clampi(src_floor(ur1, 0.25) + 2, 0, S.h - 1);
+            const int ac0 = clampi(src_floor(uc0, 0.25) - 1, 0, S.w - 1), ac1 = clampi(src_floor(uc1, 0.25) + 2, 0, S.w - 1);
+            const int an = ar1 - ar0 + 1, am = ac1 - ac0 + 1;
+            stage_flip_average<T>(S.net, b, c, cf, ns, P.flip, S.h, S.w, ar0, an, ac0, am, sA);
+            __syncthreads();
+            for (int i = threadIdx.x; i < un * um; i += 256)
+                sU[i] = resize_tap_lds(sA, ar0, ac0, am, S.h, S.w, 0.25, 0.25, ur0 + i / um, uc0 + i % um);
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int dy = oy0 + ly + 8 * k, dx = ox0 + lx;
+                if (dy < oy1 && dx < ox1) {
+                    const float v = S.identity ? sU[(dy - ur0) * um + (dx - uc0)]
+                                               : resize_tap_lds(sU, ur0, uc0, um, S.ch, S.cw, S.sx, S.sy, dy, dx);
+                    acc[k] = __dadd_rn(acc[k], (double)(v / P.n_div));
+                }
+            }
+        }
+        __syncthreads();   // the tiles are rewritten by the next entry
+    }
+    double *D = c < PP_NUM_LIMB ? P.paf_acc + ((long)b * PP_NUM_LIMB + c) * P.img_h * P.img_w
+                                : P.heat_acc + ((long)b * PP_NUM_HEAT + (c - PP_NUM_LIMB)) * P.img_h * P.img_w;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int dy = oy0 + ly + 8 * k, dx = ox0 + lx;
+        if (dy < oy1 && dx < ox1) D[(long)dy * P.img_w + dx] = acc[k];
+    }
+}
+
+// cv2.warpAffine(src, M, (0, 0)) of float32 maps (the chain's step between the x4 map and the crop, and predict_refactor's
+// feature-resolution maps): hwc = 0: n planes (n, h, w); hwc = 1: (n, h, w, C) interleaved.  One thread per output value.
+__global__ __launch_bounds__(256) void k_warp_affine_f32(const float *__restrict__ src, float *__restrict__ dst, long n, int h,
+                                                         int w, int C, int hwc, const Affine6 M) {
+    const long total = n * h * w * (hwc ? C : 1);
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        int c = 0, x, y;
+        long t = i;
+        if (hwc) {
+            c = (int)(t % C);
+            t /= C;
+        }
+        x = (int)(t % w);
+        t /= w;
+        y = (int)(t % h);
+        const long p = t / h;
+        const AffineTap tp = affine_tap(M.m, x, y);
+        float v = 0.0f;
+        if (!affine_outside(tp, h, w)) {
+            const long cs = hwc ? C : 1, base = hwc ? p * h * w * C + c : p * h * w;
+            float q[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int ty = tp.sy + (k >> 1), tx = tp.sx + (k & 1);
+                q[k] = (ty >= 0 && ty < h && tx >= 0 && tx < w) ? src[base + ((long)ty * w + tx) * cs] : 0.0f;
+            }
+            v = affine_combine(tp, q[0], q[1], q[2], q[3]);
+        }
+        dst[i] = v;
     }
 }
 
@@ -3727,6 +3976,93 @@ hipError_t launch_accumulate_scales(int n_scales, const void *const *nets, int d
     const dim3 grid(((img_w + kAccTile - 1) / kAccTile) * ((img_h + kAccTile - 1) / kAccTile), PP_NUM_CH, batch);
     if (dtype == PP_F16) hipLaunchKernelGGL(k_accumulate_scales<__half>, grid, dim3(256), lds, stream, P);
     else hipLaunchKernelGGL(k_accumulate_scales<float>, grid, dim3(256), lds, stream, P);
+    return hipGetLastError();
+}
+
+// The rotation search's form: m_inv[i] (HOST, 6 doubles, or NULL = entry i is not rotated).  No rotated entry: the launch above,
+// unchanged.  LDS per rotated entry is bounded on the host from the inverted matrix: the pre-image of the W region (rr x rc)
+// spans |m0| (rc - 1) + |m1| (rr - 1) columns and |m3| (rc - 1) + |m4| (rr - 1) rows of U, plus slack for the fixed-point
+// rounding and the bilinear taps.
+hipError_t launch_accumulate_scales_affine(int n_scales, const void *const *nets, int dtype, int batch, const int *hs, const int *ws,
+                                           int flip, const int *pad_down, const int *pad_right, const double *const *m_inv,
+                                           int img_h, int img_w, double *heat_acc, double *paf_acc, hipStream_t stream) {
+    bool any = false;
+    for (int i = 0; i < n_scales && m_inv; i++) any = any || m_inv[i] != nullptr;
+    if (!any)
+        return launch_accumulate_scales(n_scales, nets, dtype, batch, hs, ws, flip, pad_down, pad_right, img_h, img_w, heat_acc,
+                                        paf_acc, stream);
+    if (n_scales < 1 || n_scales > kAccMaxScales) return hipErrorInvalidValue;
+    AccParamsWarp P;
+    P.n = n_scales;
+    P.flip = flip;
+    P.img_h = img_h;
+    P.img_w = img_w;
+    P.n_div = (float)n_scales;
+    P.heat_acc = heat_acc;
+    P.paf_acc = paf_acc;
+    long umax = 0, amax = 0, wmax = 0, rmax = 0, cmax = 0;
+    for (int i = 0; i < n_scales; i++) {
+        AccScaleWarp &S = P.s[i];
+        S.net = nets[i];
+        S.h = hs[i];
+        S.w = ws[i];
+        S.ch = 4 * hs[i] - pad_down[i];
+        S.cw = 4 * ws[i] - pad_right[i];
+        if (S.ch <= 0 || S.cw <= 0) return hipErrorInvalidValue;
+        S.identity = (S.ch == img_h && S.cw == img_w) ? 1 : 0;
+        S.sx = 1.0 / ((double)img_w / (double)S.cw);
+        S.sy = 1.0 / ((double)img_h / (double)S.ch);
+        const int ur = S.identity ? kAccTile : (int)(kAccTile * S.sy) + 6, uc = S.identity ? kAccTile : (int)(kAccTile * S.sx) + 6;
+        S.warp = m_inv[i] ? 1 : 0;
+        for (int k = 0; k < 6; k++) S.m[k] = m_inv[i] ? m_inv[i][k] : 0.0;
+        if (!S.warp) {
+            const int ar = ur / 4 + 6, ac = uc / 4 + 6;
+            umax = std::max(umax, (long)ur * uc);
+            amax = std::max(amax, (long)ar * ac);
+            continue;
+        }
+        const double *m = m_inv[i];
+        {   // forward matrix: the inverse of m_inv, as posepaf/rotation.py invert_affine computes it
+            double f[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
+            double D = f[0] * f[4] - f[1] * f[3];
+            D = D != 0.0 ? 1.0 / D : 0.0;
+            const double a11 = f[4] * D, a22 = f[0] * D;
+            f[0] = a11, f[1] *= -D, f[3] *= -D, f[4] = a22;
+            const double b1 = -f[0] * f[2] - f[1] * f[5], b2 = -f[3] * f[2] - f[4] * f[5];
+            f[2] = b1, f[5] = b2;
+            for (int k = 0; k < 6; k++) S.fwd[k] = (float)f[k];
+        }
+        rmax = std::max(rmax, (long)ur);
+        cmax = std::max(cmax, (long)uc);
+        const double bw = std::fabs(m[0]) * (uc - 1) + std::fabs(m[1]) * (ur - 1), bh = std::fabs(m[3]) * (uc - 1) + std::fabs(m[4]) * (ur - 1);
+        if (!(bw < 1e6 && bh < 1e6)) return hipErrorInvalidValue;
+        const long br = std::min((long)std::ceil(bh) + 8, 4L * hs[i]), bc = std::min((long)std::ceil(bw) + 8, 4L * ws[i]);
+        const long ar = std::min(br / 4 + 6, (long)hs[i]), ac = std::min(bc / 4 + 6, (long)ws[i]);
+        umax = std::max(umax, br * bc);
+        amax = std::max(amax, ar * ac);
+        wmax = std::max(wmax, (long)ur * uc);
+    }
+    wmax = (wmax + 1) & ~1L;   // the int2 row / column terms that follow sW stay 8-byte aligned
+    const size_t lds = ((size_t)umax + amax + wmax) * sizeof(float) + (size_t)(rmax + cmax) * sizeof(int2);
+    if (lds > 60000) return hipErrorInvalidValue;
+    P.u_cap = (int)umax;
+    P.a_cap = (int)amax;
+    P.w_cap = (int)wmax;
+    P.r_cap = (int)rmax;
+    const dim3 grid(((img_w + kAccTile - 1) / kAccTile) * ((img_h + kAccTile - 1) / kAccTile), PP_NUM_CH, batch);
+    if (dtype == PP_F16) hipLaunchKernelGGL(k_accumulate_scales_affine<__half>, grid, dim3(256), lds, stream, P);
+    else hipLaunchKernelGGL(k_accumulate_scales_affine<float>, grid, dim3(256), lds, stream, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_warp_affine_f32(const float *src, float *dst, long n, int h, int w, int channels, int hwc, const double *m_inv,
+                                  hipStream_t stream) {
+    Affine6 M;
+    for (int k = 0; k < 6; k++) M.m[k] = m_inv[k];
+    const long total = n * h * w * (hwc ? channels : 1);
+    long blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(k_warp_affine_f32, dim3(blocks), dim3(256), 0, stream, src, dst, n, h, w, channels, hwc, M);
     return hipGetLastError();
 }
 

@@ -74,6 +74,11 @@ def parse(argv=None):
     ap.add_argument("--scales", type=float, nargs="*", default=None,
                     help="without --run_refactor: predict's `multiplier` list (the reference hard-codes [1.0], "
                          "utils/parse_skeletons.py:188); e.g. 0.5 1.0 1.5 for BASELINE config 5")
+    ap.add_argument("--rotation_search", type=float, nargs="+", default=None, metavar="A",
+                    help="without --run_refactor: test-time rotation angles in degrees (the INI's rotation_search, "
+                         "utils/config_reader.py:23); every (scale, angle) entry is run and averaged.  Default 0 (no rotation). "
+                         "--run_refactor refuses a non-zero angle: the reference's refactored path keeps only the last angle's "
+                         "maps, rotated about a misplaced centre, and the batched graph engine does not implement that")
     return ap.parse_args(argv)
 
 
@@ -302,11 +307,17 @@ def run_original(a, src, mine, model, post, dev):
     with a real scale search.  Accumulators live at image resolution, so images are bucketed by exact size; per batch the images
     are decoded by a thread pool into a pinned buffer (uploaded while the previous batch computes), every scale runs
     resize -> pad / normalise / mirror -> forward, and ALL scales are accumulated by one launch (pp_original_accumulate_all).
-    Synthetic runs take their scenes from a device-resident bank per scale (64 scenes), like the refactored path."""
+    With --rotation_search every (scale, angle) entry is one more forward: the padded input is rotated by the pre-processing
+    kernel and the entry's x4 maps are warped back inside the same launch (pp_original_accumulate_all_affine).
+    Synthetic runs take their scenes from a device-resident bank per (scale, angle) (64 scenes), like the refactored path;
+    a rotated entry's scenes are rendered at the rotated positions (synth.make_scene_at_scales)."""
     from concurrent.futures import ThreadPoolExecutor
     from posepaf.original_path import OriginalPathProcessor, resize_images_u8, scaled_size
     from posepaf.pipeline import preprocess_batch
+    from posepaf.rotation import input_and_map_inverses
     B, scales = a.batch, a.scales or [1.0]
+    angles = [float(v) for v in (a.rotation_search or [0.0])]
+    n_div = len(scales) * len(angles)
     shapes = [src.shape(int(i)) for i in mine]
     groups = {}
     for k, hw in enumerate(shapes):
@@ -324,9 +335,11 @@ def run_original(a, src, mine, model, post, dev):
                 model(x)
                 if src.has_scenes:
                     fh, fw = x.shape[1] // 4, x.shape[2] // 4
-                    arr = np.stack([synth.make_scene_at_scales(src.n_people(s_), 20_000 + s_, [(fh, fw, float(sc))], img=H)[0][0]
-                                    for s_ in range(SCENE_BANK)])
-                    banks[(H, W, float(sc))] = torch.from_numpy(arr).to(dev)
+                    for ang in angles:
+                        entry = (fh, fw, float(sc)) if ang == 0.0 else (fh, fw, float(sc), ang)
+                        arr = np.stack([synth.make_scene_at_scales(src.n_people(s_), 20_000 + s_, [entry], img=H)[0][0]
+                                        for s_ in range(SCENE_BANK)])
+                        banks[(H, W, float(sc), ang)] = torch.from_numpy(arr).to(dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     copy_stream = torch.cuda.Stream(device=dev)
@@ -367,12 +380,14 @@ def run_original(a, src, mine, model, post, dev):
                 for sc in scales:
                     scaled = resize_images_u8(dev_imgs, float(sc))
                     sh, sw = scaled.shape[1:3]
-                    x = preprocess_batch(scaled, True, torch.float16)
-                    ph, pw = x.shape[1:3]
-                    maps = model(x).contiguous().view(B, 2, 50, ph // 4, pw // 4)
-                    if src.has_scenes:   # the same synthetic people, rendered at this scale
-                        maps = torch.addcmul(banks[(H, W, float(sc))].index_select(0, slots), maps, scale)
-                    proc.accumulate(maps, ph - sh, pw - sw, len(scales))
+                    for ang in angles:
+                        m_in, m_rev = input_and_map_inverses(*padded_shape(sh, sw), ang)
+                        x = preprocess_batch(scaled, True, torch.float16, m_inv=m_in)
+                        ph, pw = x.shape[1:3]
+                        maps = model(x).contiguous().view(B, 2, 50, ph // 4, pw // 4)
+                        if src.has_scenes:   # the same synthetic people, rendered at this scale (and rotation)
+                            maps = torch.addcmul(banks[(H, W, float(sc), ang)].index_select(0, slots), maps, scale)
+                        proc.accumulate(maps, ph - sh, pw - sw, n_div, m_inv=m_rev)
                 rec = proc.finish(B)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
@@ -381,7 +396,10 @@ def run_original(a, src, mine, model, post, dev):
             stage(j + 1)                            # the next batch is decoded and uploaded while this one computes
     torch.cuda.synchronize()
     pool.shutdown(wait=False)
-    return local.view(-1), time.perf_counter() - t0, {"launch": "eager", "scales": scales, "decode_threads": workers}
+    info = {"launch": "eager", "scales": scales, "decode_threads": workers}
+    if a.rotation_search is not None:
+        info["rotation_search"] = angles
+    return local.view(-1), time.perf_counter() - t0, info
 
 
 def main(argv=None):
@@ -402,6 +420,9 @@ def main(argv=None):
     original = not a.run_refactor   # evaluate.py:81-84: predict + find_peaks + find_connections + find_humans
     if original and a.run_cpp:
         raise SystemExit("--run_cpp only exists on the refactored path (evaluate.py:97-129)")
+    if not original and any(float(v) != 0.0 for v in (a.rotation_search or [])):
+        raise SystemExit("--rotation_search with a non-zero angle runs on the original path only (drop --run_refactor): the "
+                         "reference's refactored path returns the last angle's maps alone, rotated about a misplaced centre")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

@@ -18,20 +18,32 @@ from .api import PosePostProcessor, records_to_numpy
 from .fused_model import to_planes
 
 
-def preprocess_batch(images_u8: torch.Tensor, flip: bool = True, dtype=torch.float32) -> torch.Tensor:
+def preprocess_batch(images_u8: torch.Tensor, flip: bool = True, dtype=torch.float32, m_inv=None) -> torch.Tensor:
     """utils/parse_skeletons.py:52-73 + utils/util.py:44-65 for a batch of equally sized images (scale 1):
     uint8 BGR (B,H,W,3) -> pad bottom/right to a multiple of 64 with 128 -> /255 -> NHWC in [0,1], each image followed
     by the W-mirror of the padded image -> (2B,Hp,Wp,3).  One HIP kernel (pp_preprocess_u8) on the GPU.
     `np.float32(img / 255)` is a float64 division rounded to float32; float32(x)/255 in float32 is the same
-    correctly rounded quotient for every x in 0..255 (checked exhaustively in tests/test_pipeline_cpu.py)."""
+    correctly rounded quotient for every x in 0..255 (checked exhaustively in tests/test_pipeline_cpu.py).
+    m_inv (2x3 / 6 doubles, posepaf.rotation): the padded image is rotated with cv2.warpAffine before the mirror
+    (:214-221), by pp_preprocess_u8_affine; GPU only.  None: the unrotated kernel, unchanged."""
     B, H, W, _ = images_u8.shape
     Hp = -(-H // sk.MAX_DOWNSAMPLE) * sk.MAX_DOWNSAMPLE
     Wp = -(-W // sk.MAX_DOWNSAMPLE) * sk.MAX_DOWNSAMPLE
+    if m_inv is not None and not (images_u8.is_cuda and dtype in (torch.float16, torch.float32)):
+        raise ValueError("the rotated pre-processing runs on the GPU only (uint8 device images, float16 / float32 output)")
     if images_u8.is_cuda and dtype in (torch.float16, torch.float32):
         import ctypes as C
         from . import _lib
         images_u8 = images_u8.contiguous()
         out = torch.empty((B * (2 if flip else 1), Hp, Wp, 3), dtype=dtype, device=images_u8.device)
+        if m_inv is not None:
+            from .rotation import as_c_doubles
+            rc = _lib.load().pp_preprocess_u8_affine(C.c_void_p(images_u8.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                     _lib.PP_F16 if dtype == torch.float16 else _lib.PP_F32, B, H, W,
+                                                     sk.MAX_DOWNSAMPLE, sk.PAD_VALUE, int(flip), as_c_doubles(m_inv),
+                                                     C.c_void_p(torch.cuda.current_stream(images_u8.device).cuda_stream))
+            _lib.check(rc)
+            return out
         rc = _lib.load().pp_preprocess_u8(C.c_void_p(images_u8.data_ptr()), C.c_void_p(out.data_ptr()),
                                           _lib.PP_F16 if dtype == torch.float16 else _lib.PP_F32, B, H, W, sk.MAX_DOWNSAMPLE,
                                           sk.PAD_VALUE, int(flip),

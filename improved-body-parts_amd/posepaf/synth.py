@@ -146,16 +146,32 @@ def make_scene(n_people: int, seed: int, h: int = 128, w: int = 128, noise: floa
     return np.ascontiguousarray(out.astype(dtype)), joints
 
 
+def rotate_joints(joints: np.ndarray, m) -> np.ndarray:
+    """joints (P, 18, 3) with x / y pushed through the 2x3 matrix m (flags kept)"""
+    from .rotation import apply_affine
+    out = joints.copy()
+    out[:, :, :2] = apply_affine(m, joints[:, :, :2])
+    return out
+
+
 def make_scene_at_scales(n_people: int, seed: int, sizes, noise: float = 0.02, dtype=np.float16, p_missing: float = 0.08,
                          img: int = 512):
     """The SAME people rendered on feature maps of several sizes (a scale search): -> (list of (2,50,h,w) outputs, joints).
-    sizes: list of (h, w, scale) with the map showing the image scaled by `scale` (top-left aligned, padding beyond)."""
+    sizes: list of (h, w, scale) or (h, w, scale, angle) with the map showing the image scaled by `scale` (top-left aligned,
+    padding beyond).  With a non-zero angle the scaled joints are first rotated by the FORWARD matrix the reference rotates
+    its padded input with (getRotationMatrix2D about the swapped centre of the (4h, 4w) padded frame, posepaf.rotation), so
+    that after the inverse warp of the maps (predict, utils/parse_skeletons.py:265-267) the people land where they are."""
     rng = np.random.default_rng(seed)
     joints = random_people(n_people, rng, img_h=img, img_w=img, p_missing=p_missing)
     outs = []
-    for (h, w, scale) in sizes:
+    for entry in sizes:
+        h, w, scale = entry[:3]
+        angle = float(entry[3]) if len(entry) > 3 else 0.0
         j = joints.copy()
         j[:, :, :2] *= scale
+        if angle != 0.0:
+            from .rotation import reference_center, rotation_matrix
+            j = rotate_joints(j, rotation_matrix(reference_center(STRIDE * h, STRIDE * w), angle))
         base = render_maps(j, h, w)
         out = np.stack([base, mirror_sample(base)]).astype(np.float32)
         if noise > 0:

@@ -48,14 +48,25 @@ def _post(h, w):
 
 def predict_refactor(image, model, test_cfg, model_cfg, input_image_path, flip_avg=True, config=None):
     """BGR uint8 (H, W, 3) -> (heatmap_avg (h, w, 20), paf_avg (h, w, 30)) float32, h = padded H / 4.
-    Scale search is fixed to [1.0] as in the reference (:36); rotation_search must be [0]."""
-    if any(a != 0 for a in test_cfg.get("rotation_search", [0.0])):
-        raise NotImplementedError("rotation_search != 0 is not supported (the reference's default is 0)")
+    Scale search is fixed to [1.0] as in the reference (:36).
+
+    rotation_search (:46-102), with the reference's two quirks kept:
+    * heatmap_avg / paf_avg are OVERWRITTEN per angle (:101-102), not averaged: only the LAST angle's result is returned, so
+      only the last angle is run here -- the earlier ones cannot change the output;
+    * the flip-averaged FEATURE-resolution maps (h, w) are warped with M_rev computed for the padded INPUT shape (:64-65,
+      :98-100): the rotation centre is 4x off on the feature map (and swapped, posepaf.rotation.reference_center).
+    The reference hands cv2.warpAffine the flip-average in the model's dtype (binary16 under AMP); here the binary16
+    flip-average is widened to float32 first (pp_flip_average's output) and that is warped (pp_warp_affine_f32, HWC)."""
+    from posepaf.rotation import input_and_map_inverses
+    angle = float(list(test_cfg.get("rotation_search", [0.0]))[-1])
     dev = next(model.parameters()).device
     dtype = next(model.parameters()).dtype
     img = torch.from_numpy(np.ascontiguousarray(image)).to(dev)[None]
+    hp = -(-img.shape[1] // sk.MAX_DOWNSAMPLE) * sk.MAX_DOWNSAMPLE
+    wp = -(-img.shape[2] // sk.MAX_DOWNSAMPLE) * sk.MAX_DOWNSAMPLE
+    m_in, m_rev = input_and_map_inverses(hp, wp, angle)
     with torch.no_grad():
-        x = preprocess_batch(img, True, dtype if dtype in (torch.float16, torch.float32) else torch.float32)
+        x = preprocess_batch(img, True, dtype if dtype in (torch.float16, torch.float32) else torch.float32, m_inv=m_in)
         out = model(x)
         maps = to_planes(out[-1][0] if isinstance(out, (list, tuple)) else out)   # (2, 50, h, w)
     h, w = maps.shape[-2:]
@@ -65,9 +76,19 @@ def predict_refactor(image, model, test_cfg, model_cfg, input_image_path, flip_a
     if maps.dtype not in (torch.float16, torch.float32):
         maps, code = maps.float(), _lib.PP_F32
     src = maps if flip_avg else maps[:1].contiguous()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(_lib.load().pp_flip_average(C.c_void_p(src.data_ptr()), code, 1, h, w, int(bool(flip_avg)),
-                                           C.c_void_p(heat.data_ptr()), C.c_void_p(paf.data_ptr()),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                           C.c_void_p(heat.data_ptr()), C.c_void_p(paf.data_ptr()), st))
+    if m_rev is not None:
+        from posepaf.rotation import as_c_doubles
+        mr = as_c_doubles(m_rev)
+        out = []
+        for t in (heat, paf):
+            r = torch.empty_like(t)
+            _lib.check(_lib.load().pp_warp_affine_f32(C.c_void_p(t.data_ptr()), C.c_void_p(r.data_ptr()), 1, h, w, t.shape[2], 1,
+                                                      mr, st))
+            out.append(r)
+        heat, paf = out
     return heat.cpu().numpy(), paf.cpu().numpy()
 
 
@@ -123,10 +144,11 @@ def _original(img_h, img_w):
 def predict(image, model, test_cfg, model_cfg, input_image_path, flip_avg=True, config=None):
     """utils/parse_skeletons.py:180-283: BGR uint8 (H, W, 3) -> (heatmap_avg (H, W, 20), paf_avg (H, W, 30)) float64 at IMAGE
     resolution.  The scale list is [1.0], as the reference fixes it at :188 (its `scale_search` line :186 is dead);
-    `test_cfg["multiplier"]`, when present, overrides it (BASELINE config 5 uses 0.5 / 1.0 / 1.5).  rotation_search must be [0]."""
-    if any(a != 0 for a in test_cfg.get("rotation_search", [0.0])):
-        raise NotImplementedError("rotation_search != 0 is not supported (the reference's default is 0)")
+    `test_cfg["multiplier"]`, when present, overrides it (BASELINE config 5 uses 0.5 / 1.0 / 1.5).  Every (scale, angle) of
+    product(multiplier, rotation_search) is one entry (:196); a non-zero angle rotates the padded input (:214-218) and warps
+    the x4 maps back before the crop (:265-267); each entry is divided by len(multiplier) * len(rotation_search) (:280-281)."""
     from posepaf.original_path import resize_images_u8
+    from posepaf.rotation import input_and_map_inverses
     img_h, img_w = image.shape[:2]
     proc = _original(img_h, img_w)
     dev = next(model.parameters()).device
@@ -134,20 +156,26 @@ def predict(image, model, test_cfg, model_cfg, input_image_path, flip_avg=True, 
     dtype = dtype if dtype in (torch.float16, torch.float32) else torch.float32
     img = torch.from_numpy(np.ascontiguousarray(image)).to(dev)[None]
     multiplier = [float(m) for m in test_cfg.get("multiplier", [1.0])]
+    angles = [float(a) for a in test_cfg.get("rotation_search", [0.0])]
+    n_div = len(multiplier) * len(angles)
     with torch.no_grad():
         proc.reset()
         for scale in multiplier:
             scaled = resize_images_u8(img, scale)                          # cv2.resize(image, fx=scale), :204
             sh, sw = scaled.shape[1:3]
-            x = preprocess_batch(scaled, True, dtype)                      # pad to /64 with 128, /255, mirror (:206-226)
-            out = model(x)
-            maps = to_planes(out[-1][0] if isinstance(out, (list, tuple)) else out)
-            if maps.dtype not in (torch.float16, torch.float32):
-                maps = maps.float()
-            maps = maps.view(1, 2, sk.NUM_CH, maps.shape[-2], maps.shape[-1])
-            if not flip_avg:
-                maps = maps[:, :1].contiguous()                            # :236-237 the un-mirrored sample alone
-            proc.accumulate(maps, x.shape[1] - sh, x.shape[2] - sw, len(multiplier), flip=bool(flip_avg))
+            for angle in angles:
+                hp = -(-sh // sk.MAX_DOWNSAMPLE) * sk.MAX_DOWNSAMPLE
+                wp = -(-sw // sk.MAX_DOWNSAMPLE) * sk.MAX_DOWNSAMPLE
+                m_in, m_rev = input_and_map_inverses(hp, wp, angle)
+                x = preprocess_batch(scaled, True, dtype, m_inv=m_in)      # pad to /64 with 128, /255, rotate, mirror (:206-226)
+                out = model(x)
+                maps = to_planes(out[-1][0] if isinstance(out, (list, tuple)) else out)
+                if maps.dtype not in (torch.float16, torch.float32):
+                    maps = maps.float()
+                maps = maps.view(1, 2, sk.NUM_CH, maps.shape[-2], maps.shape[-1])
+                if not flip_avg:
+                    maps = maps[:, :1].contiguous()                        # :236-237 the un-mirrored sample alone
+                proc.accumulate(maps, x.shape[1] - sh, x.shape[2] - sw, n_div, flip=bool(flip_avg), m_inv=m_rev)
     heat = proc.heat_acc[0].permute(1, 2, 0).contiguous().cpu().numpy()
     paf = proc.paf_acc[0].permute(1, 2, 0).contiguous().cpu().numpy()
     return heat, paf

@@ -291,6 +291,11 @@ PP_API int pp_stem7x7_f16(const void *x, const void *w_prepared, const void *bia
  * followed (flip != 0) by the W-mirror of the PADDED image.  out: DEVICE (batch*(flip?2:1), Hp, Wp, 3), PP_F16 or PP_F32. */
 PP_API int pp_preprocess_u8(const void *images_u8, void *out, int dtype, int batch, int h, int w, int pad_to,
                             int pad_value, int flip, void *stream);
+/* The same with the test-time rotation (utils/parse_skeletons.py:214-221): the padded image is warped with cv2.warpAffine(M,
+ * (0, 0)) -- m_inv: HOST, 6 doubles, M inverted as warpAffine does it (posepaf/rotation.py) -- 0 outside the padded frame,
+ * and the mirror written is that of the WARPED image. */
+PP_API int pp_preprocess_u8_affine(const void *images_u8, void *out, int dtype, int batch, int h, int w, int pad_to,
+                                   int pad_value, int flip, const double *m_inv, void *stream);
 /* The same for a bucket of images of DIFFERENT sizes sharing one padded shape (hp, wp) -- the reference pads every image
  * alone (utils/parse_skeletons.py:54); the batched evaluation loop groups images by padded shape.  images_u8: DEVICE
  * (batch, hp, wp, 3), image b in the top-left (sizes[b], sizes[batch + b]) corner of its slot, the rest of the slot is never
@@ -361,6 +366,25 @@ PP_API int pp_original_accumulate(pp_ctx *ctx, int batch, const void *net_out_de
 PP_API int pp_original_accumulate_all(pp_ctx *ctx, int batch, int n_scales, const void *const *net_out_dev, int dtype, const int *h,
                                       const int *w, int flip, const int *pad_down, const int *pad_right, int img_h, int img_w,
                                       double *heat_acc, double *paf_acc, void *stream);
+/* Test-time rotation search (utils/parse_skeletons.py:180-283 with rotation_search != [0]): every (scale, angle) entry is one
+ * more accumulation, the x4 map of a rotated entry warped back with cv2.warpAffine(M_rev, (0, 0)) before the crop.  m_inv: HOST,
+ * 6 doubles, the matrix INVERTED as warpAffine does it (posepaf/rotation.py); sampling is OpenCV's fixed-point INTER_LINEAR with
+ * BORDER_CONSTANT 0 (posepaf_affine.h).  pp_original_accumulate_affine: one entry through the chain, += value / n_div; m_inv
+ * NULL is pp_original_accumulate; scratch_warp float[batch][50][4h][4w].  pp_original_accumulate_all_affine: every entry in ONE
+ * launch (written, not added to, as pp_original_accumulate_all), m_inv: HOST array of n_entries pointers, NULL = not rotated;
+ * n_div = n_entries; bit-identical to the chain; PP_ERR_UNSUPPORTED beyond 6 entries or when an entry's tiles do not fit LDS. */
+PP_API int pp_original_accumulate_affine(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip,
+                                         int pad_down, int pad_right, int img_h, int img_w, int n_div, const double *m_inv,
+                                         float *scratch_planar, float *scratch_up, float *scratch_warp, double *heat_acc,
+                                         double *paf_acc, void *stream);
+PP_API int pp_original_accumulate_all_affine(pp_ctx *ctx, int batch, int n_entries, const void *const *net_out_dev, int dtype,
+                                             const int *h, const int *w, int flip, const int *pad_down, const int *pad_right,
+                                             const double *const *m_inv, int img_h, int img_w, double *heat_acc, double *paf_acc,
+                                             void *stream);
+/* cv2.warpAffine(src, M, (0, 0)) of DEVICE float32 maps, m_inv as above: hwc = 0: n planes (n, h, w); hwc = 1: (n, h, w,
+ * channels) interleaved.  dst (same shape) must not alias src. */
+PP_API int pp_warp_affine_f32(const float *src, float *dst, long n, int h, int w, int channels, int hwc, const double *m_inv,
+                              void *stream);
 PP_API int pp_original_finish(pp_ctx *ctx, int batch, int img_h, int img_w, float thre1, const double *heat_acc,
                               const double *paf_acc, unsigned char *mask_scratch, void *peaks64_scratch, pp_record *records_dev,
                               void *stream);
