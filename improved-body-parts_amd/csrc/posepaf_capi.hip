@@ -5,6 +5,7 @@
 // index bookkeeping) and moves bytes.  There is no CPU implementation to fall back to.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,6 +44,10 @@ struct pp_ctx {
     std::vector<int> line_x, line_y;
     std::vector<float> line_s;
     bool have_result = false;
+    // run-time test configuration of the Python rules; cfg_default: the launchers get NULL and run the literal instances
+    pp_test_cfg cfg = {0.1, 0.8, 16.0, 0.7, 20, 2, 0};
+    bool cfg_default = true;
+    const pp_test_cfg *py_cfg() const { return cfg_default ? nullptr : &cfg; }
 };
 
 namespace {
@@ -102,7 +107,7 @@ const char *pp_status_string(int status) {
         case PP_ERR_TOO_LARGE: return "batch or map size beyond the context's capacity / LDS";
         case PP_ERR_HIP: return "HIP runtime error (see pp_last_hip_error)";
         case PP_ERR_OVERFLOW: return "capacity exceeded (peaks per part or humans)";
-        case PP_ERR_UNSUPPORTED: return "shape not supported by this convolution tile configuration";
+        case PP_ERR_UNSUPPORTED: return "shape not supported by this convolution tile configuration, or test configuration value out of range";
         default: return "unknown status";
     }
 }
@@ -238,9 +243,9 @@ int pp_process_batch_py(pp_ctx *ctx, int batch, const void *net_out_dev, int dty
                                       ctx->d_counts, ctx->d_status, nullptr, nullptr, st));
     PP_HIP(ctx, pp::launch_limb_connect_py(net_out_dev, dtype, batch, ns, h, w, flip, ctx->maxp, ctx->cap, img_height,
                                            img_height_dev, ctx->d_peaks, ctx->d_counts, ctx->d_conns_py, ctx->d_conn_counts,
-                                           ctx->d_status, st));
+                                           ctx->d_status, ctx->py_cfg(), st));
     PP_HIP(ctx, pp::launch_assemble_py(batch, ctx->maxp, 0, ctx->d_peaks, ctx->d_counts, ctx->d_conns_py, ctx->d_conn_counts,
-                                       ctx->d_status, 0, rec, nullptr, nullptr, st));
+                                       ctx->d_status, 0, rec, nullptr, nullptr, ctx->py_cfg(), st));
     ctx->last_stream = st;
     ctx->last_batch = batch;
     ctx->last_peaks = ctx->d_peaks;
@@ -576,9 +581,39 @@ int pp_original_finish(pp_ctx *ctx, int batch, int img_h, int img_w, float thre1
     hipStream_t st = static_cast<hipStream_t>(stream);
     pp_record *rec = records_dev ? records_dev : ctx->d_records;
     PP_HIP(ctx, pp::launch_fullres(batch, img_h, img_w, thre1, ctx->maxp, ctx->cap, img_h, heat_acc, paf_acc, mask_scratch,
-                                   peaks64_scratch, ctx->d_counts, ctx->d_conns_py, ctx->d_conn_counts, ctx->d_status, rec, st));
+                                   peaks64_scratch, ctx->d_counts, ctx->d_conns_py, ctx->d_conn_counts, ctx->d_status, rec,
+                                   ctx->py_cfg(), st));
     ctx->last_stream = st;
     ctx->last_batch = batch;
+    return PP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ run-time test configuration
+int pp_default_test_cfg(pp_test_cfg *cfg) {
+    if (!cfg) return PP_ERR_BAD_ARG;
+    *cfg = pp_test_cfg{0.1, 0.8, 16.0, 0.7, 20, 2, 0};
+    return PP_OK;
+}
+
+int pp_set_test_cfg(pp_ctx *ctx, const pp_test_cfg *cfg) {
+    if (!ctx || !cfg) return PP_ERR_BAD_ARG;
+    for (double v : {cfg->thre2, cfg->connect_ration, cfg->len_rate, cfg->connection_tole})
+        if (!std::isfinite(v) || v < 0.0) return PP_ERR_UNSUPPORTED;
+    if (cfg->mid_num < 1 || cfg->mid_num > 128 || cfg->offset_radius < 0 || cfg->offset_radius > 7 ||
+        (cfg->remove_recon != 0 && cfg->remove_recon != 1))
+        return PP_ERR_UNSUPPORTED;
+    pp_test_cfg d;
+    pp_default_test_cfg(&d);
+    ctx->cfg = *cfg;
+    ctx->cfg_default = cfg->thre2 == d.thre2 && cfg->connect_ration == d.connect_ration && cfg->len_rate == d.len_rate &&
+                       cfg->connection_tole == d.connection_tole && cfg->mid_num == d.mid_num &&
+                       cfg->offset_radius == d.offset_radius && cfg->remove_recon == d.remove_recon;
+    return PP_OK;
+}
+
+int pp_get_test_cfg(const pp_ctx *ctx, pp_test_cfg *cfg) {
+    if (!ctx || !cfg) return PP_ERR_BAD_ARG;
+    *cfg = ctx->cfg;
     return PP_OK;
 }
 
@@ -628,7 +663,7 @@ int pp_py_find_connections_host(pp_ctx *ctx, const float *peaks, int n, const fl
     PP_HIP(ctx, hipMemcpyAsync(ctx->d_peaks, pk.data(), pk.size() * sizeof(float4), hipMemcpyHostToDevice, st));
     PP_HIP(ctx, hipMemcpyAsync(ctx->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice, st));
     PP_HIP(ctx, pp::launch_limb_connect_py_hwc(ctx->d_paf, H, W, C, maxp, ctx->cap, img_height, ctx->d_peaks, ctx->d_counts,
-                                               ctx->d_conns_py, ctx->d_conn_counts, ctx->d_status, st));
+                                               ctx->d_conns_py, ctx->d_conn_counts, ctx->d_status, ctx->py_cfg(), st));
     std::vector<double> raw((size_t)PP_NUM_LIMB * maxp * 4);
     PP_HIP(ctx, hipMemcpyAsync(raw.data(), ctx->d_conns_py, raw.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     PP_HIP(ctx, hipMemcpyAsync(counts_out, ctx->d_conn_counts, sizeof(int) * PP_NUM_LIMB, hipMemcpyDeviceToHost, st));
@@ -691,7 +726,7 @@ int pp_py_find_humans_host(pp_ctx *ctx, const double *conns, const int *counts_l
     PP_HIP(ctx, hipMemcpyAsync(ctx->d_conn_counts, cl, sizeof(cl), hipMemcpyHostToDevice, st));
     PP_HIP(ctx, pp::launch_assemble_py(1, maxp, 1, ctx->d_peaks, ctx->d_counts, ctx->d_conns_py, ctx->d_conn_counts,
                                        ctx->d_status, pp::kFlagWordsPerImage, ctx->d_records, ctx->d_persons, ctx->d_npersons,
-                                       st));  // connections come from the caller: no kernel wrote a flag word
+                                       ctx->py_cfg(), st));  // connections come from the caller: no kernel wrote a flag word
     int np = 0;
     PP_HIP(ctx, hipMemcpyAsync(&np, ctx->d_npersons, sizeof(int), hipMemcpyDeviceToHost, st));
     PP_HIP(ctx, hipStreamSynchronize(st));

@@ -43,17 +43,19 @@ hipError_t launch_assemble(int batch, int maxp, int explicit_ids, const float4 *
                            const float4 *conns, const int *conn_counts, const unsigned *status, int flag_first,
                            pp_record *records, hipStream_t stream);
 
+// The Python-twin launchers take the context's test configuration (cfg; NULL = the INI defaults).  Each kernel's general
+// instance is launched only when a value IT reads differs from the default; otherwise the instance with the literals runs.
 size_t lds_bytes_limb_py(int elem, int h, int w, int maxp, int cap);
 size_t lds_bytes_assemble_py(int maxp);
 hipError_t launch_limb_connect_py(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, int maxp,
                                   int cap, int img_height, const int *img_height_dev, const float4 *peaks, const int *counts,
-                                  void *conns, int *conn_counts, unsigned *status, hipStream_t stream);
+                                  void *conns, int *conn_counts, unsigned *status, const pp_test_cfg *cfg, hipStream_t stream);
 hipError_t launch_assemble_py(int batch, int maxp, int explicit_ids, const float4 *peaks, const int *counts, const void *conns,
                               const int *conn_counts, const unsigned *status, int flag_first, pp_record *records,
-                              double *persons_out, int *n_persons_out, hipStream_t stream);
+                              double *persons_out, int *n_persons_out, const pp_test_cfg *cfg, hipStream_t stream);
 hipError_t launch_limb_connect_py_hwc(const float *paf, int H, int W, int C, int maxp, int cap, int img_height,
                                       const float4 *peaks, const int *counts, void *conns, int *conn_counts, unsigned *status,
-                                      hipStream_t stream);
+                                      const pp_test_cfg *cfg, hipStream_t stream);
 
 hipError_t launch_resize_cubic(const float *src, long src_plane, int src_ld, int ch, int cw, void *dst, int acc, int C, int dh,
                                int dw, double scale_x, double scale_y, float n_div, hipStream_t stream);
@@ -69,7 +71,7 @@ hipError_t launch_warp_affine_f32(const float *src, float *dst, long n, int h, i
                                   hipStream_t stream);
 hipError_t launch_fullres(int batch, int H, int W, float thre1, int maxp, int cap, int img_height, const double *heat_acc,
                           const double *paf_acc, unsigned char *mask_scratch, void *peaks64, int *counts, void *conns,
-                          int *conn_counts, unsigned *status, pp_record *records, hipStream_t stream);
+                          int *conn_counts, unsigned *status, pp_record *records, const pp_test_cfg *cfg, hipStream_t stream);
 
 }  // namespace pp
 #endif

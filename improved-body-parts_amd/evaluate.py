@@ -4,6 +4,8 @@
     python evaluate.py --run_refactor --run_cpp --synthetic 5000 [--batch 128] [--dump_name results.json]
     python evaluate.py --run_refactor --run_cpp -p weights.pth --ann_file person_keypoints_val2017.json --img_dir val2017
     python evaluate.py --gpus 8 --run_refactor --run_cpp --synthetic 5000          # launches its own 8 ranks
+    python evaluate.py --synthetic 512 --batch 32 --scales 1.0 --test_cfg thre2=0.05 mid_num=40 remove_recon=1   # original
+        path with the reference's test_cfg keys as run-time values (or --config_file PATH: the [param] section of an INI file)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --synthetic 5000 ...
 
 What is kept from the reference: the flags --run_refactor / --run_cpp (:53-54; --run_cpp selects the C++ pafprocess rules --
@@ -42,7 +44,7 @@ if HERE not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from posepaf import coco, dist as pdist, oks_eval, synth  # noqa: E402
+from posepaf import coco, dist as pdist, oks_eval, skeleton as sk, synth  # noqa: E402
 from posepaf._lib import RECORD_BYTES  # noqa: E402
 from posepaf.engine import padded_shape  # noqa: E402
 
@@ -79,7 +81,24 @@ def parse(argv=None):
                          "utils/config_reader.py:23); every (scale, angle) entry is run and averaged.  Default 0 (no rotation). "
                          "--run_refactor refuses a non-zero angle: the reference's refactored path keeps only the last angle's "
                          "maps, rotated about a misplaced centre, and the batched graph engine does not implement that")
-    return ap.parse_args(argv)
+    ap.add_argument("--test_cfg", nargs="+", default=None, metavar="KEY=VALUE",
+                    help="without --run_refactor: run-time values of the reference's test_cfg (utils/config [param]) read by "
+                         "find_peaks / find_connections / find_humans: thre1 thre2 connect_ration mid_num len_rate connection_tole "
+                         "offset_radius remove_recon, e.g. --test_cfg thre2=0.05 mid_num=40 remove_recon=1.  The C++ pafprocess "
+                         "rules (--run_cpp) have these compiled in, as in the reference, and refuse the option")
+    ap.add_argument("--config_file", default=None, metavar="PATH",
+                    help="without --run_refactor: take those values from the [param] section of a file in the reference's INI "
+                         "layout (utils/config); --test_cfg entries override it")
+    a = ap.parse_args(argv)
+    a.test_cfg_dict = None
+    if a.test_cfg is not None or a.config_file is not None:
+        try:
+            cfg = sk.read_config_file(a.config_file) if a.config_file else {}
+            cfg.update(sk.parse_test_cfg_items(a.test_cfg))
+            a.test_cfg_dict = sk.merge_test_cfg(cfg)
+        except (ValueError, OSError) as e:
+            ap.error(str(e))
+    return a
 
 
 def buckets_by_padded_shape(shapes):
@@ -318,6 +337,10 @@ def run_original(a, src, mine, model, post, dev):
     B, scales = a.batch, a.scales or [1.0]
     angles = [float(v) for v in (a.rotation_search or [0.0])]
     n_div = len(scales) * len(angles)
+    thre1 = 0.1
+    if a.test_cfg_dict is not None:
+        post.set_test_cfg(a.test_cfg_dict)
+        thre1 = a.test_cfg_dict["thre1"]
     shapes = [src.shape(int(i)) for i in mine]
     groups = {}
     for k, hw in enumerate(shapes):
@@ -388,7 +411,7 @@ def run_original(a, src, mine, model, post, dev):
                         if src.has_scenes:   # the same synthetic people, rendered at this scale (and rotation)
                             maps = torch.addcmul(banks[(H, W, float(sc), ang)].index_select(0, slots), maps, scale)
                         proc.accumulate(maps, ph - sh, pw - sw, n_div, m_inv=m_rev)
-                rec = proc.finish(B)
+                rec = proc.finish(B, thre1)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
             events[k][1] = done
@@ -399,6 +422,7 @@ def run_original(a, src, mine, model, post, dev):
     info = {"launch": "eager", "scales": scales, "decode_threads": workers}
     if a.rotation_search is not None:
         info["rotation_search"] = angles
+    info["test_cfg"] = post.test_cfg      # the configuration in force, read back from the context
     return local.view(-1), time.perf_counter() - t0, info
 
 
@@ -423,6 +447,12 @@ def main(argv=None):
     if not original and any(float(v) != 0.0 for v in (a.rotation_search or [])):
         raise SystemExit("--rotation_search with a non-zero angle runs on the original path only (drop --run_refactor): the "
                          "reference's refactored path returns the last angle's maps alone, rotated about a misplaced centre")
+    if a.test_cfg_dict is not None and a.run_cpp:
+        raise SystemExit("--test_cfg / --config_file configure the Python rules; the C++ pafprocess rules (--run_cpp) have their "
+                         "constants compiled in, as in the reference (utils/pafprocess/pafprocess.h:6-18)")
+    if a.test_cfg_dict is not None and not original:
+        raise SystemExit("--test_cfg / --config_file run on the original path only (drop --run_refactor): the refactored path's "
+                         "captured graphs are built for the INI defaults")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -517,6 +547,8 @@ def main(argv=None):
                    "images_per_gpu_per_step": a.batch, "rules": "original" if original else ("cpp" if a.run_cpp else "python"),
                    "people_found": len(results),
                    "status_or": int(np.bitwise_or.reduce(merged["status"])) if len(merged) else 0}
+        if summary["status_or"] & 128:   # PP_ST_RECON_UNDEFINED: remove_recon met a case where the reference itself raises
+            summary["recon_undefined_images"] = int(np.count_nonzero(merged["status"] & 128))
         summary.update(info)
         if gts:
             key = "keypoint_ap" if src.gts else "synthetic_oks"     # ground truth from the annotation file / from the injected scenes

@@ -16,7 +16,8 @@ PP_F32, PP_F16 = 0, 1
 
 ST_PEAK_OVERFLOW, ST_HUMAN_OVERFLOW, ST_SKEL_OVERFLOW, ST_SORT_UNDEFINED, ST_CAND_OVERFLOW, ST_FLOAT_COORDS = 1, 2, 4, 8, 16, 32
 ST_SYNC_TIMEOUT = 64
-ST_DEFINED_MASK = 0x7F            # include/posepaf.h:53-61; any other bit in pp_record.status is corruption
+ST_RECON_UNDEFINED = 128          # remove_recon = 1: the reference raises on a connection of this image (nothing changed)
+ST_DEFINED_MASK = 0xFF            # include/posepaf.h:53-61; any other bit in pp_record.status is corruption
 ST_OVERFLOW_MASK = ST_PEAK_OVERFLOW | ST_HUMAN_OVERFLOW | ST_SKEL_OVERFLOW | ST_CAND_OVERFLOW
 
 # numpy views of pp_human / pp_record (include/posepaf.h)
@@ -32,7 +33,7 @@ EXPORTS = [
     "pp_get_num_humans", "pp_get_part_peak_id", "pp_get_score", "pp_get_part_x", "pp_get_part_y",
     "pp_get_part_score", "pp_get_status", "pp_py_find_connections_host", "pp_py_find_humans_host", "pp_original_accumulate", "pp_original_accumulate_all", "pp_original_finish",
     "pp_preprocess_u8_affine", "pp_original_accumulate_affine", "pp_original_accumulate_all_affine", "pp_warp_affine_f32",
-    "pp_resize_u8_cubic",
+    "pp_resize_u8_cubic", "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -55,6 +56,12 @@ def build(verbose: bool = False) -> str:
     if verbose:
         print(r.stdout)
     return LIB_PATH
+
+
+class TestCfg(C.Structure):
+    """pp_test_cfg (include/posepaf.h)"""
+    _fields_ = [("thre2", C.c_double), ("connect_ration", C.c_double), ("len_rate", C.c_double),
+                ("connection_tole", C.c_double), ("mid_num", C.c_int), ("offset_radius", C.c_int), ("remove_recon", C.c_int)]
 
 
 def load():
@@ -124,6 +131,9 @@ def load():
     dp = C.POINTER(C.c_double)
     L.pp_py_find_connections_host.argtypes = [vp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, ip, ip]
     L.pp_py_find_humans_host.argtypes = [vp, dp, ip, fp, C.c_int, dp, C.c_int, ip]
+    L.pp_default_test_cfg.argtypes = [C.POINTER(TestCfg)]
+    L.pp_set_test_cfg.argtypes = [vp, C.POINTER(TestCfg)]
+    L.pp_get_test_cfg.argtypes = [vp, C.POINTER(TestCfg)]
     L.pp_original_accumulate.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, vp, vp, vp, vp, vp]
     L.pp_original_accumulate_all.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, ip, ip, C.c_int, ip, ip, C.c_int, C.c_int,

@@ -119,6 +119,27 @@ class PosePostProcessor:
                                           int(flip), int(min_img_size), int(iters), ms, C.c_void_p(stream)), self.ctx)
         return {"k_heat_peaks": ms[0], "k_limb_connect": ms[1], "k_assemble_wave": ms[2], "chain": ms[3]}
 
+    def set_test_cfg(self, cfg=None):
+        """pp_set_test_cfg: the run-time values of the Python rules (thre2, connect_ration, mid_num, len_rate, connection_tole,
+        offset_radius, remove_recon) for process_py and the original path; `cfg` holds the keys to move off the INI defaults
+        (None / {} = the defaults).  process (the C++ pafprocess rules) never reads it.  An out-of-range value raises and
+        leaves the previous configuration in force.  thre1, when present, is kept for OriginalPathProcessor (it travels as
+        pp_original_finish's argument)."""
+        from . import skeleton as sk
+        full = sk.merge_test_cfg(cfg)
+        packed = _lib.TestCfg(*sk.pack_test_cfg(full))
+        _lib.check(self.L.pp_set_test_cfg(self.ctx, C.byref(packed)), self.ctx)
+        self._thre1 = full["thre1"]
+
+    @property
+    def test_cfg(self) -> dict:
+        """the configuration in force (pp_get_test_cfg), as a dict with the keys of skeleton.TEST_CFG_KEYS"""
+        c = _lib.TestCfg()
+        _lib.check(self.L.pp_get_test_cfg(self.ctx, C.byref(c)), self.ctx)
+        return {"thre1": getattr(self, "_thre1", 0.1), "thre2": c.thre2, "connect_ration": c.connect_ration,
+                "len_rate": c.len_rate, "connection_tole": c.connection_tole, "mid_num": c.mid_num,
+                "offset_radius": c.offset_radius, "remove_recon": c.remove_recon}
+
     def set_mode(self, mode: int):
         """pp_debug_set_mode: 0 fused + load-ordered (default), 1 separate assembly launch, 2 fused without ordering"""
         _lib.check(self.L.pp_debug_set_mode(self.ctx, int(mode)), self.ctx)

@@ -165,8 +165,14 @@ class OriginalPathProcessor:
         for m, pdn, prt, n, f, mi in pend:
             self._chain(m, pdn, prt, n, f, mi)
 
-    def finish(self, batch: int, thre1: float = 0.1) -> torch.Tensor:
+    def finish(self, batch: int, thre1: float = 0.1, test_cfg=None) -> torch.Tensor:
+        """test_cfg: None = what the post-processor's context holds; a dict = set it on the context first (keys moved off the
+        INI defaults, see PosePostProcessor.set_test_cfg) and take thre1 from it when it has one."""
         self._flush()
+        if test_cfg is not None:
+            self.post.set_test_cfg(test_cfg)
+            if "thre1" in test_cfg:
+                thre1 = float(test_cfg["thre1"])
         st = C.c_void_p(torch.cuda.current_stream(self._heat.device).cuda_stream)
         _lib.check(_lib.load().pp_original_finish(self.post.ctx, batch, self.H, self.W, float(thre1), _p(self._heat),
                                                   _p(self._paf), _p(self.mask), _p(self.peaks64), _p(self.records), st),
@@ -175,7 +181,7 @@ class OriginalPathProcessor:
 
     @torch.no_grad()
     def run(self, model, images_u8: torch.Tensor, multiplier, dtype=torch.float16, thre1: float = 0.1,
-            angles=(0.0,)) -> np.ndarray:
+            angles=(0.0,), test_cfg=None) -> np.ndarray:
         """images (B, H, W, 3) uint8 on the GPU -> records (float coordinates, PP_ST_FLOAT_COORDS).
         Every (scale, angle) of product(multiplier, angles) is one entry (utils/parse_skeletons.py:196), each divided by
         len(multiplier) * len(angles); angle 0 takes the unrotated steps."""
@@ -194,7 +200,7 @@ class OriginalPathProcessor:
                 maps = to_planes(out[-1][0] if isinstance(out, (list, tuple)) else out)
                 maps = maps.view(B, 2, sk.NUM_CH, maps.shape[-2], maps.shape[-1])
                 self.accumulate(maps, ph - sh, pw - sw, n_div, m_inv=m_rev)
-        return records_to_numpy(self.finish(B, thre1))
+        return records_to_numpy(self.finish(B, thre1, test_cfg))
 
 
 def record_float_coords(rec):

@@ -62,6 +62,94 @@ def default_test_cfg():
     }
 
 
+# the keys of test_cfg that are run-time values of the batched Python-rule paths (pp_test_cfg, include/posepaf.h), with their
+# types; thre1 travels as pp_original_finish's argument
+TEST_CFG_KEYS = {"thre1": float, "thre2": float, "connect_ration": float, "len_rate": float, "connection_tole": float,
+                 "mid_num": int, "offset_radius": int, "remove_recon": int}
+TEST_CFG_MID_NUM_MAX = 128       # NumPy's pairwise-sum block: above it mean() recurses
+TEST_CFG_OFFSET_RADIUS_MAX = 7   # a (2r+1)^2 box within four values per lane of one wave
+
+
+def merge_test_cfg(cfg=None, base=None):
+    """Validated copy of `base` (default: default_test_cfg()) with the entries of `cfg` applied.  Only TEST_CFG_KEYS may be
+    moved; a key outside them may be present when it holds its default (a full reference `param` dict passes).  Integer keys
+    take integral values only (the INI's `len_rate = 16` is an int there and a float here: both are fine for float keys)."""
+    import math
+    out = dict(default_test_cfg() if base is None else base)
+    defaults = default_test_cfg()
+    for key, val in dict(cfg or {}).items():
+        if key not in TEST_CFG_KEYS:
+            if key in defaults and val == defaults[key]:
+                continue
+            raise ValueError(f"test_cfg[{key!r}] is not a run-time value of the batched paths "
+                             f"(those are: {', '.join(sorted(TEST_CFG_KEYS))})")
+        if isinstance(val, bool) or not isinstance(val, (int, float, np.integer, np.floating)):
+            raise ValueError(f"test_cfg[{key!r}] must be a number, got {val!r}")
+        if TEST_CFG_KEYS[key] is int:
+            if float(val) != int(val):
+                raise ValueError(f"test_cfg[{key!r}] must be an integer, got {val!r}")
+            out[key] = int(val)
+        else:
+            out[key] = float(val)
+            if not math.isfinite(out[key]) or out[key] < 0.0:
+                raise ValueError(f"test_cfg[{key!r}] must be finite and >= 0, got {val!r}")
+    if not 1 <= out["mid_num"] <= TEST_CFG_MID_NUM_MAX:
+        raise ValueError(f"test_cfg['mid_num'] must be in 1..{TEST_CFG_MID_NUM_MAX}, got {out['mid_num']}")
+    if not 0 <= out["offset_radius"] <= TEST_CFG_OFFSET_RADIUS_MAX:
+        raise ValueError(f"test_cfg['offset_radius'] must be in 0..{TEST_CFG_OFFSET_RADIUS_MAX}, got {out['offset_radius']}")
+    if out["remove_recon"] not in (0, 1):
+        raise ValueError(f"test_cfg['remove_recon'] must be 0 or 1, got {out['remove_recon']}")
+    return out
+
+
+def pack_test_cfg(cfg=None):
+    """cfg dict -> the pp_test_cfg fields in declaration order (thre2, connect_ration, len_rate, connection_tole, mid_num,
+    offset_radius, remove_recon), validated by merge_test_cfg."""
+    c = merge_test_cfg(cfg)
+    return (c["thre2"], c["connect_ration"], c["len_rate"], c["connection_tole"], c["mid_num"], c["offset_radius"],
+            c["remove_recon"])
+
+
+def parse_test_cfg_items(items):
+    """['thre2=0.05', 'mid_num=40'] -> {'thre2': 0.05, 'mid_num': 40} (keys of TEST_CFG_KEYS only)"""
+    out = {}
+    for item in items or []:
+        key, sep, val = item.partition("=")
+        key = key.strip()
+        if not sep or key not in TEST_CFG_KEYS:
+            raise ValueError(f"--test_cfg takes KEY=VALUE with KEY in {sorted(TEST_CFG_KEYS)}, got {item!r}")
+        try:
+            out[key] = TEST_CFG_KEYS[key](val.strip()) if TEST_CFG_KEYS[key] is float else int(val.strip(), 10)
+        except ValueError:
+            raise ValueError(f"--test_cfg {item!r}: {val!r} is not a valid {TEST_CFG_KEYS[key].__name__}") from None
+    return out
+
+
+def read_config_file(path):
+    """The run-time keys of the [param] section of a file in the reference's INI layout (`key = value  # comment` lines under
+    `[param]`, other sections and nested `[[n]]` sections ignored) -> dict for merge_test_cfg.  Keys that are not run-time
+    values of the batched paths (scale_search, crop_ratio, ...) are skipped."""
+    out, section = {}, None
+    with open(path, encoding="utf-8") as f:
+        for raw in f:
+            line = raw.split("#", 1)[0].strip()
+            if not line:
+                continue
+            if line.startswith("["):
+                section = line.strip("[]").strip() if not line.startswith("[[") else None
+                continue
+            if section != "param" or "=" not in line:
+                continue
+            key, _, val = line.partition("=")
+            key, val = key.strip(), val.strip()
+            if key in TEST_CFG_KEYS:
+                try:
+                    out[key] = float(val) if TEST_CFG_KEYS[key] is float else int(val, 10)
+                except ValueError:
+                    raise ValueError(f"{path}: [param] {key} = {val!r} is not a valid {TEST_CFG_KEYS[key].__name__}") from None
+    return out
+
+
 def default_model_cfg():
     """`model` dict of utils/config_reader.py (utils/config [[1]] section), typed."""
     return {"boxsize": BOXSIZE, "padValue": PAD_VALUE, "np": "12", "stride": STRIDE,

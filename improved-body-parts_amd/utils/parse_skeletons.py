@@ -227,7 +227,10 @@ def _joint_rows(all_peaks):
 
 
 def _ctx():
-    """context for the host-form twins: 64 peaks per part (the float64 person table + connections must fit LDS)"""
+    """context for the host-form twins: 64 peaks per part (the float64 person table + connections must fit LDS).
+    It is this module's own and nothing here calls set_test_cfg on it: the shims keep running the INI defaults (_check_cfg
+    refuses anything else) whatever configuration another processor's context holds.  Configured runs go through
+    PosePostProcessor.set_test_cfg / OriginalPathProcessor / evaluate.py --test_cfg."""
     from posepaf.api import PosePostProcessor
     if "py" not in _post_cache:
         _post_cache["py"] = PosePostProcessor(max_batch=1, max_h=sk.BOXSIZE // sk.STRIDE, max_w=sk.BOXSIZE // sk.STRIDE,

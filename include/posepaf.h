@@ -59,6 +59,9 @@ typedef enum { PP_F32 = 0, PP_F16 = 1 } pp_dtype;
 #define PP_ST_FLOAT_COORDS 32u   /* original path: pp_human.x / .y hold float32 BIT PATTERNS (fractional coordinates) */
 #define PP_ST_SYNC_TIMEOUT 64u   /* the image's assembly gave up waiting for a limb of its own launch (cannot happen on a healthy
                                     device: the record is incomplete and the context must be re-created) */
+#define PP_ST_RECON_UNDEFINED 128u /* Python rules with remove_recon = 1: for a connection of this image the reference itself raises
+                                    (utils/parse_skeletons.py:529-537: int(np.where(...)[0]) on zero or several matches, or
+                                    the assert conn1_idx != conn2_idx); that connection changed nothing */
 
 /* One person.  Mirrors what evaluate.py:111-127 pulls through the getters:
  * peak_id[p] = get_part_peak_id(h,p) (-1 = part absent); x/y/part_score = get_part_x/y/score(peak_id);
@@ -390,6 +393,32 @@ PP_API int pp_original_finish(pp_ctx *ctx, int batch, int img_h, int img_w, floa
                               void *stream);
 PP_API int pp_resize_u8_cubic(const void *src, void *dst, int batch, int sh, int sw, int dh, int dw, double scale_x,
                               double scale_y, void *stream);
+
+/* ---------------------------------------------------------------- run-time test configuration (Python rules)
+ * The matching rules the reference's Python post-processing reads from test_cfg (utils/config:16-27,
+ * utils/parse_skeletons.py:309, :328-329, :353, :429-431, :530).  thre1 is not here: it stays pp_original_finish's argument.
+ * Read by pp_process_batch_py, pp_original_finish, pp_py_find_connections_host and pp_py_find_humans_host.
+ * pp_process_batch (the C++ pafprocess rules) never looks at it: the reference compiles those constants in.
+ * With the defaults the kernels with the literals run, exactly as before; a general instance of a kernel is launched only
+ * when a value that kernel reads differs from its default. */
+typedef struct {
+    double thre2;           /* 0.1   limb-map threshold of a sample; compared as NumPy does: a float32 map in float32 with
+                                      the value rounded once, a float64 map in double */
+    double connect_ration;  /* 0.8   count(samples > thre2) > mid_num * connect_ration */
+    double len_rate;        /* 16    a new limb may be at most len_rate times the person's longest so far */
+    double connection_tole; /* 0.7   merge of two disjoint people: score >= connection_tole * min limb score */
+    int mid_num;            /* 20    samples per candidate limb, 1..128.  128 is NumPy's pairwise-sum block: up to there mean()
+                                      is the eight-accumulator loop the kernels restate, above it NumPy recurses */
+    int offset_radius;      /* 2     refine_centroid's radius (original path), 0..7: the (2r+1)^2 box, at most 225 values, must
+                                      fit one 64-lane wave four times over (up to four values per lane) */
+    int remove_recon;       /* 0     0 / 1: take a joint shared by two people away from the weaker one (:526-564) */
+} pp_test_cfg;
+/* the INI defaults above */
+PP_API int pp_default_test_cfg(pp_test_cfg *cfg);
+/* A fresh context holds the defaults.  PP_ERR_UNSUPPORTED, context unchanged: mid_num outside 1..128, offset_radius outside
+ * 0..7, remove_recon not 0 / 1, a non-finite or negative thre2 / connect_ration / len_rate / connection_tole. */
+PP_API int pp_set_test_cfg(pp_ctx *ctx, const pp_test_cfg *cfg);
+PP_API int pp_get_test_cfg(const pp_ctx *ctx, pp_test_cfg *cfg);
 
 /* ---------------------------------------------------------------- Python twins, host form
  * utils.parse_skeletons.find_connections / find_humans (:324-600) with host arrays, for callers of the non --run_cpp
