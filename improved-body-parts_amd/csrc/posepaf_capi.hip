@@ -28,6 +28,9 @@ struct pp_ctx {
                                   // 16 words | per-limb publication flags [max_batch][30] (see k_limb_connect); then: K_A's
                                   // grid-wide ticket; zeroed ONCE here, re-armed by the kernels themselves (no memset node)
     int mode = 0;                 // pp_debug_set_mode
+    void *d_maps = nullptr;       // [max_batch][48][plane stride] flip-averaged maps of shapes that do not fit LDS (k_flip_average_maps);
+    size_t d_maps_bytes = 0;      // allocated at create only when an fp32 max_h x max_w map would not fit, or by pp_set_map_residency
+    int residency = PP_MAPS_AUTO; // pp_set_map_residency
     unsigned *d_status = nullptr; // [max_batch][48] flag words, one per producing workgroup (posepaf_kernels.hip or_flags)
     void *d_conns_py = nullptr;   // [max_batch][30][maxp] double4 (src, dst, score, length): Python-twin path
     double *d_persons = nullptr;  // [128][40] raw person table of the Python-twin host form
@@ -77,15 +80,69 @@ void free_ctx(pp_ctx *c) {
     (void)hipFree(c->d_npersons);
     (void)hipFree(c->d_records);
     (void)hipFree(c->d_paf);
+    (void)hipFree(c->d_maps);
     delete c;
 }
 
-int check_shape(const pp_ctx *c, int batch, int dtype, int h, int w) {
+// capacity: what the context was created for
+int check_capacity(const pp_ctx *c, int batch, int dtype, int h, int w) {
     if (!c || batch <= 0 || h <= 0 || w <= 0 || (dtype != PP_F16 && dtype != PP_F32)) return PP_ERR_BAD_ARG;
     if (batch > c->max_batch || (size_t)h * w > (size_t)c->max_h * c->max_w) return PP_ERR_TOO_LARGE;
+    return PP_OK;
+}
+
+bool fits_lds(const pp_ctx *c, int dtype, int h, int w) {
     const int elem = dtype == PP_F16 ? 2 : 4;
-    if (pp::lds_bytes_heat(elem, h, w, c->maxp) > pp::kMaxDynLds) return PP_ERR_TOO_LARGE;
-    if (pp::lds_bytes_limb(elem, h, w, c->maxp, c->cap) > pp::kMaxDynLds) return PP_ERR_TOO_LARGE;
+    return pp::lds_bytes_heat(elem, h, w, c->maxp) <= pp::kMaxDynLds && pp::lds_bytes_limb(elem, h, w, c->maxp, c->cap) <= pp::kMaxDynLds;
+}
+
+// residency: where the kernels keep the map of a shape that passed check_capacity -- PP_MAPS_LDS (today's launches), PP_MAPS_HBM
+// (pre-pass + the _hbm instances), or PP_ERR_TOO_LARGE when neither can take it
+int decide_residency(const pp_ctx *c, int dtype, int h, int w) {
+    if (c->residency == PP_MAPS_AUTO && fits_lds(c, dtype, h, w)) return PP_MAPS_LDS;
+    if ((size_t)h * w > pp::kMaxHbmPixels || !c->d_maps || pp::map_workspace_bytes(c->max_batch, h, w) > c->d_maps_bytes ||
+        pp::lds_bytes_heat_hbm(h, w, c->maxp, c->max_batch) > pp::kMaxDynLds || pp::lds_bytes_limb_hbm(c->maxp, c->cap) > pp::kMaxDynLds)
+        return PP_ERR_TOO_LARGE;
+    return PP_MAPS_HBM;
+}
+
+// the Python-rule entry keeps the whole map in LDS: capacity, then the LDS bound
+int check_shape(const pp_ctx *c, int batch, int dtype, int h, int w) {
+    const int rc = check_capacity(c, batch, dtype, h, w);
+    if (rc != PP_OK) return rc;
+    return fits_lds(c, dtype, h, w) ? PP_OK : PP_ERR_TOO_LARGE;
+}
+
+// capacity check + residency decision of the C++-rule entries; *hbm = the decision
+int check_shape_resident(const pp_ctx *c, int batch, int dtype, int h, int w, bool *hbm) {
+    int rc = check_capacity(c, batch, dtype, h, w);
+    if (rc != PP_OK) return rc;
+    rc = decide_residency(c, dtype, h, w);
+    if (rc < 0) return rc;
+    *hbm = rc == PP_MAPS_HBM;
+    return PP_OK;
+}
+
+// pp_process_batch for a map that stays in HBM: three launches -- the flip-average pre-pass, then K_A and K_B reading its
+// workspace.  Same workspaces, flags and ctx->mode meanings as the LDS form; the image sorter has LDS of its own here.
+int process_batch_hbm(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip, int min_img_size,
+                      const int *min_img_size_dev, pp_record *rec, hipStream_t st) {
+    int *order = ctx->d_sync, *arrive = ctx->d_sync + ctx->max_batch, *arrive_all = ctx->d_sync + 2 * ctx->max_batch;
+    const bool sorted = ctx->mode == 0;
+    PP_HIP(ctx, pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st));
+    PP_HIP(ctx, pp::launch_heat_peaks_hbm(ctx->d_maps, dtype, batch, h, w, 1, 0, 0.1f, ctx->maxp, ctx->d_peaks, ctx->d_counts,
+                                          ctx->d_status, sorted ? order : nullptr, sorted ? arrive_all : nullptr, st));
+    PP_HIP(ctx, pp::launch_limb_connect_hbm(ctx->d_maps, dtype, batch, h, w, ctx->maxp, ctx->cap, min_img_size, min_img_size_dev,
+                                            ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux, ctx->d_conn_counts,
+                                            ctx->d_status, sorted ? order : nullptr, ctx->mode == 1 ? nullptr : arrive,
+                                            reinterpret_cast<unsigned *>(ctx->d_sync + 2 * ctx->max_batch + 16), rec, st));
+    if (ctx->mode == 1)
+        PP_HIP(ctx, pp::launch_assemble_wave(batch, ctx->maxp, ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux,
+                                             ctx->d_conn_counts, ctx->d_status, rec, st));
+    ctx->last_stream = st;
+    ctx->last_batch = batch;
+    ctx->last_peaks = ctx->d_peaks;
+    ctx->last_counts = ctx->d_counts;
     return PP_OK;
 }
 
@@ -104,7 +161,9 @@ const char *pp_status_string(int status) {
         case PP_OK: return "ok";
         case PP_ERR_NO_DEVICE: return "no HIP device (this library has no CPU path)";
         case PP_ERR_BAD_ARG: return "bad argument";
-        case PP_ERR_TOO_LARGE: return "batch or map size beyond the context's capacity / LDS";
+        case PP_ERR_TOO_LARGE:
+            return "batch or map size beyond the context's capacity (or beyond LDS on the Python-rule path, which has no "
+                   "large-map kernels yet, or beyond 650x950)";
         case PP_ERR_HIP: return "HIP runtime error (see pp_last_hip_error)";
         case PP_ERR_OVERFLOW: return "capacity exceeded (peaks per part or humans)";
         case PP_ERR_UNSUPPORTED: return "shape not supported by this convolution tile configuration, or test configuration value out of range";
@@ -147,6 +206,11 @@ int pp_create(pp_ctx **out, int device, int max_batch, int max_h, int max_w, int
     if (e == hipSuccess) e = hipMemset(c->d_counts, 0, B * PP_NUM_PART * sizeof(int));
     if (e == hipSuccess) e = hipMemset(c->d_conn_counts, 0, B * PP_NUM_LIMB * sizeof(int));
     if (e == hipSuccess) e = hipMemset(c->d_status, 0, B * pp::kFlagWordsPerImage * sizeof(unsigned));
+    // the flip-averaged map workspace of shapes beyond LDS: only contexts whose largest fp32 map would not fit pay for it
+    if (e == hipSuccess && !fits_lds(c, PP_F32, max_h, max_w)) {
+        c->d_maps_bytes = pp::map_workspace_bytes(max_batch, max_h, max_w);
+        e = hipMalloc(&c->d_maps, c->d_maps_bytes);
+    }
     if (e != hipSuccess) {
         free_ctx(c);
         return PP_ERR_HIP;
@@ -174,6 +238,25 @@ int pp_debug_set_stamps(long long *stamps_dev) {
     return pp::set_stamp_buffer(stamps_dev) == hipSuccess ? PP_OK : PP_ERR_HIP;
 }
 
+int pp_set_map_residency(pp_ctx *ctx, int mode) {
+    if (!ctx || (mode != PP_MAPS_AUTO && mode != PP_MAPS_HBM)) return PP_ERR_BAD_ARG;
+    if (mode == PP_MAPS_HBM && !ctx->d_maps) {
+        PP_HIP(ctx, hipSetDevice(ctx->device));
+        const size_t bytes = pp::map_workspace_bytes(ctx->max_batch, ctx->max_h, ctx->max_w);
+        PP_HIP(ctx, hipMalloc(&ctx->d_maps, bytes));
+        ctx->d_maps_bytes = bytes;
+    }
+    ctx->residency = mode;
+    return PP_OK;
+}
+
+int pp_map_residency(const pp_ctx *ctx, int dtype, int h, int w) {
+    const int rc = check_capacity(ctx, 1, dtype, h, w);
+    return rc != PP_OK ? rc : decide_residency(ctx, dtype, h, w);
+}
+
+long long pp_map_workspace_bytes(const pp_ctx *ctx) { return ctx ? (long long)ctx->d_maps_bytes : 0; }
+
 int pp_nms_batch(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip, int refine,
                  float *peaks_dev, int *counts_dev, void *stream) {
     return pp_nms_batch_ex(ctx, batch, net_out_dev, dtype, h, w, flip, 0, 0.1f, refine ? 1 : 0, peaks_dev, counts_dev, stream);
@@ -181,15 +264,22 @@ int pp_nms_batch(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int
 
 int pp_nms_batch_ex(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip, int nms_mode,
                     float threshold, int refine_mode, float *peaks_dev, int *counts_dev, void *stream) {
-    int rc = check_shape(ctx, batch, dtype, h, w);
+    bool hbm = false;
+    int rc = check_shape_resident(ctx, batch, dtype, h, w, &hbm);
     if (rc != PP_OK) return rc;
     if (!net_out_dev || nms_mode < 0 || nms_mode > 1 || refine_mode < 0 || refine_mode > 3) return PP_ERR_BAD_ARG;
     const int refine = refine_mode;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float4 *pk = peaks_dev ? reinterpret_cast<float4 *>(peaks_dev) : ctx->d_peaks;
     int *cn = counts_dev ? counts_dev : ctx->d_counts;
-    PP_HIP(ctx, pp::launch_heat_peaks(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, refine, nms_mode, threshold,
-                                      ctx->maxp, pk, cn, ctx->d_status, nullptr, nullptr, st));
+    if (hbm) {
+        PP_HIP(ctx, pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st));
+        PP_HIP(ctx, pp::launch_heat_peaks_hbm(ctx->d_maps, dtype, batch, h, w, refine, nms_mode, threshold, ctx->maxp, pk, cn,
+                                              ctx->d_status, nullptr, nullptr, st));
+    } else {
+        PP_HIP(ctx, pp::launch_heat_peaks(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, refine, nms_mode, threshold,
+                                          ctx->maxp, pk, cn, ctx->d_status, nullptr, nullptr, st));
+    }
     ctx->last_stream = st;
     ctx->last_batch = batch;
     ctx->last_peaks = pk;
@@ -199,12 +289,14 @@ int pp_nms_batch_ex(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, 
 
 int pp_process_batch(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip,
                      int min_img_size, const int *min_img_size_dev, pp_record *records_dev, void *stream) {
-    int rc = check_shape(ctx, batch, dtype, h, w);
+    bool hbm = false;
+    int rc = check_shape_resident(ctx, batch, dtype, h, w, &hbm);
     if (rc != PP_OK) return rc;
     if (!net_out_dev) return PP_ERR_BAD_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     pp_record *rec = records_dev ? records_dev : ctx->d_records;
     const int ns = flip ? 2 : 1;
+    if (hbm) return process_batch_hbm(ctx, batch, net_out_dev, dtype, h, w, flip, min_img_size, min_img_size_dev, rec, st);
     // two launches: K_A (peaks; its last workgroup orders the images by load), K_B (limb scoring + matching; the last limb
     // workgroup of each image assembles it).  ctx->mode: 0 as described, 1 = K_B and the assembly as separate launches,
     // 2 = fused without the load ordering (A/B measurements, pp_debug_set_mode).
@@ -255,13 +347,15 @@ int pp_process_batch_py(pp_ctx *ctx, int batch, const void *net_out_dev, int dty
 
 int pp_time_kernels(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip,
                     int min_img_size, int iters, float *ms_out, void *stream) {
-    int rc = check_shape(ctx, batch, dtype, h, w);
+    bool hbm = false;
+    int rc = check_shape_resident(ctx, batch, dtype, h, w, &hbm);
     if (rc != PP_OK) return rc;
     if (!net_out_dev || !ms_out || iters <= 0) return PP_ERR_BAD_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int ns = flip ? 2 : 1;
     int *order = ctx->d_sync, *arrive = ctx->d_sync + ctx->max_batch, *arrive_all = ctx->d_sync + 2 * ctx->max_batch;
-    const bool sorted = ctx->mode == 0 && pp::heat_peaks_sorts(dtype, batch, h, w, ctx->maxp);
+    const bool sorted = ctx->mode == 0 && (hbm || pp::heat_peaks_sorts(dtype, batch, h, w, ctx->maxp));
+    unsigned *ready = reinterpret_cast<unsigned *>(ctx->d_sync + 2 * ctx->max_batch + 16);
     hipEvent_t e0, e1;
     PP_HIP(ctx, hipEventCreate(&e0));
     PP_HIP(ctx, hipEventCreate(&e1));
@@ -271,7 +365,15 @@ int pp_time_kernels(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, 
     for (int k = 0; k < 4; k++) {
         PP_HIP(ctx, hipEventRecord(e0, st));
         for (int i = 0; i < iters; i++) {
-            if (k == 3) {  // the whole chain, back to back, as pp_process_batch enqueues it
+            if (hbm && k == 0) {  // maps in HBM: the _hbm instances on the workspace the untimed pass filled
+                PP_HIP(ctx, pp::launch_heat_peaks_hbm(ctx->d_maps, dtype, batch, h, w, 1, 0, 0.1f, ctx->maxp, ctx->d_peaks,
+                                                      ctx->d_counts, ctx->d_status, sorted ? order : nullptr,
+                                                      sorted ? arrive_all : nullptr, st));
+            } else if (hbm && k == 1) {
+                PP_HIP(ctx, pp::launch_limb_connect_hbm(ctx->d_maps, dtype, batch, h, w, ctx->maxp, ctx->cap, min_img_size, nullptr,
+                                                        ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux, ctx->d_conn_counts,
+                                                        ctx->d_status, sorted ? order : nullptr, arrive, ready, ctx->d_records, st));
+            } else if (k == 3) {  // the whole chain, back to back, as pp_process_batch enqueues it
                 rc = pp_process_batch(ctx, batch, net_out_dev, dtype, h, w, flip, min_img_size, nullptr, nullptr, st);
                 if (rc != PP_OK) return rc;
             } else if (k == 0) {
@@ -297,6 +399,33 @@ int pp_time_kernels(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, 
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    return PP_OK;
+}
+
+int pp_time_map_prepass(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip, int iters,
+                        float *ms_out, void *stream) {
+    bool hbm = false;
+    int rc = check_shape_resident(ctx, batch, dtype, h, w, &hbm);
+    if (rc != PP_OK) return rc;
+    if (!net_out_dev || !ms_out || iters <= 0) return PP_ERR_BAD_ARG;
+    *ms_out = 0.f;
+    if (!hbm) return PP_OK;   // the map is staged in LDS: there is no pre-pass
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0.f;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st);  // untimed
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    for (int i = 0; i < iters && e == hipSuccess; i++)
+        e = pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st);
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) (void)hipEventDestroy(e0);   // on every path, failures included
+    if (e1) (void)hipEventDestroy(e1);
+    PP_HIP(ctx, e);
+    *ms_out = ms / (float)iters;
     return PP_OK;
 }
 

@@ -33,6 +33,21 @@ hipError_t launch_limb_connect(const void *net, int dtype, int batch, int n_samp
                                int cap, int min_img_size, const int *min_img_size_dev, const float4 *peaks,
                                const int *counts, float4 *conns, float4 *aux, int *conn_counts, unsigned *status,
                                const int *order, int *arrive, unsigned *ready, pp_record *records, hipStream_t stream);
+// Maps larger than LDS: launch_flip_average_maps writes the 48 used channels, flip-averaged, into
+// ws[batch][48][map_plane_stride] (element type = dtype); the _hbm launchers are K_A / K_B reading that workspace instead of LDS.
+constexpr size_t kMaxHbmPixels = (size_t)650 * 950;   // the reference's own cap on this path (utils/parse_skeletons.py:46-49), / 4
+size_t lds_bytes_heat_hbm(int h, int w, int maxp, int batch);
+size_t lds_bytes_limb_hbm(int maxp, int cap);
+size_t map_plane_stride(int elem, int h, int w);    // elements: h*w rounded up to 16 bytes
+size_t map_workspace_bytes(int batch, int h, int w);  // batch * 48 planes of fp32 + 16 bytes of slack
+hipError_t launch_flip_average_maps(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, void *ws,
+                                    hipStream_t stream);
+hipError_t launch_heat_peaks_hbm(const void *ws, int dtype, int batch, int h, int w, int refine, int nms_mode, float thr, int maxp,
+                                 float4 *peaks, int *counts, unsigned *status, int *order, int *arrive_all, hipStream_t stream);
+hipError_t launch_limb_connect_hbm(const void *ws, int dtype, int batch, int h, int w, int maxp, int cap, int min_img_size,
+                                   const int *min_img_size_dev, const float4 *peaks, const int *counts, float4 *conns, float4 *aux,
+                                   int *conn_counts, unsigned *status, const int *order, int *arrive, unsigned *ready,
+                                   pp_record *records, hipStream_t stream);
 hipError_t launch_assemble_wave(int batch, int maxp, const float4 *peaks, const int *counts, const float4 *conns,
                                 const float4 *aux, const int *conn_counts, const unsigned *status, pp_record *records,
                                 hipStream_t stream);

@@ -268,310 +268,9 @@ __device__ __forceinline__ float bicubic4_at(const T *smap, int w, int x0, int y
 
 // ------------------------------------------------------------------------------------------------ K_A
 // LDS layout (dynamic): [map: h*w T][cubic 16 f32][peak linear index i32 x maxp][peak-mask bytes x ceil(h*w/8)]
-template <typename T>
-__global__ __launch_bounds__(kThreads) void k_heat_peaks(const T *__restrict__ net, int n_samples, int h, int w,
-                                                         int flip, int refine, int nms_mode, float thr, int maxp,
-                                                         float4 *__restrict__ peaks, int *counts,
-                                                         unsigned *__restrict__ status, int *order, int *arrive_all) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int part = blockIdx.x, img = blockIdx.y;
-    const int npix = h * w;
-    size_t off = 0;
-    T *smap = reinterpret_cast<T *>(lds_raw);
-    off += (sizeof(T) * (size_t)npix + 15) & ~(size_t)15;
-    float *s_cub = reinterpret_cast<float *>(lds_raw + off);
-    off += 64;
-    int *s_pk = reinterpret_cast<int *>(lds_raw + off);
-    off += (4 * (size_t)maxp + 15) & ~(size_t)15;
-    unsigned char *s_m8 = lds_raw + off;  // one peak-mask byte per 8-pixel vector
-    __shared__ int s_wsum[kWaves];
-    __shared__ float s_hpass[kWaves][5 * 20];
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x < 16) s_cub[threadIdx.x] = d_cubic4[threadIdx.x >> 2][threadIdx.x & 3];
-
-    const size_t plane = (size_t)npix;
-    const T *o0 = net + ((size_t)img * n_samples * PP_NUM_CH + PP_NUM_LIMB + part) * plane;
-    const T *o1 = net + (((size_t)img * n_samples + 1) * PP_NUM_CH + PP_NUM_LIMB + d_flip_heat_ord[part]) * plane;
-    long long *stamps = d_stamps;
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-    stamp(stamps, wg, 0);
-    load_channel(smap, o0, o1, h, w, flip != 0);
-    __syncthreads();
-    stamp(stamps, wg, 1);
-
-    // ---- A3: local maxima.  Each lane tests 8 consecutive row-major pixels per step (one 16-byte LDS read for
-    // binary16 maps); only pixels above the threshold (a few per cent) go on to the neighbour reads.  Peak order must
-    // be np.nonzero's (ascending linear index): per-(step, wave) counts -> block prefix -> lane prefix -> bit rank.
-    const int nvec = (npix + 7) >> 3;
-    const int nk = (nvec + kThreads - 1) / kThreads;  // steps; <= kMaxSteps is checked on the host
-    const bool rows_aligned = (w & 7) == 0;  // then an 8-pixel vector never straddles two rows
-    auto mask8 = [&](int v) -> unsigned {
-        const int i0 = v << 3;
-        if (i0 >= npix) return 0u;
-        float val[8];
-        if (i0 + 8 <= npix) {
-            load8(smap + i0, val);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; j++) val[j] = i0 + j < npix ? ldsf(smap, i0 + j) : -INFINITY;
-        }
-        unsigned above = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            if (nms_mode == 0 ? (val[j] > thr) : (val[j] >= thr)) above |= 1u << j;  // parse_skeletons.py:116 / util.py:184
-        if (above == 0) return 0u;
-        unsigned m = 0;
-        if (rows_aligned) {
-            // branch-free form: the rows above/below as two more 16-byte reads, the horizontal neighbours from the
-            // vector itself plus one scalar on each side; out-of-map neighbours are -inf (never greater)
-            const int y = i0 / w, x0 = i0 - y * w;
-            float up[8], dn[8];
-            if (y > 0) load8(smap + i0 - w, up);
-            if (y < h - 1) load8(smap + i0 + w, dn);
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                if (y == 0) up[j] = -INFINITY;
-                if (y == h - 1) dn[j] = -INFINITY;
-            }
-            const float lft = x0 > 0 ? ldsf(smap, i0 - 1) : -INFINITY;
-            const float rgt = x0 + 8 < w ? ldsf(smap, i0 + 8) : -INFINITY;
-            float ul = -INFINITY, ur = -INFINITY, dl = -INFINITY, dr = -INFINITY;
-            if (nms_mode != 0) {
-                if (y > 0 && x0 > 0) ul = ldsf(smap, i0 - w - 1);
-                if (y > 0 && x0 + 8 < w) ur = ldsf(smap, i0 - w + 8);
-                if (y < h - 1 && x0 > 0) dl = ldsf(smap, i0 + w - 1);
-                if (y < h - 1 && x0 + 8 < w) dr = ldsf(smap, i0 + w + 8);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const float vj = val[j];
-                bool pk = !(up[j] > vj) && !(dn[j] > vj);
-                pk = pk && !((j > 0 ? val[j - 1] : lft) > vj) && !((j < 7 ? val[j + 1] : rgt) > vj);
-                if (nms_mode != 0) {  // full 3x3 window (utils/util.py:181-184)
-                    pk = pk && !((j > 0 ? up[j - 1] : ul) > vj) && !((j < 7 ? up[j + 1] : ur) > vj);
-                    pk = pk && !((j > 0 ? dn[j - 1] : dl) > vj) && !((j < 7 ? dn[j + 1] : dr) > vj);
-                }
-                if (pk) m |= 1u << j;
-            }
-            return m & above;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            if (above & (1u << j)) {
-                const float vj = val[j];
-                const int i = i0 + j;
-                const int y = i / w, x = i - y * w;
-                bool pk = true;
-                if (y > 0 && ldsf(smap, i - w) > vj) pk = false;
-                if (y < h - 1 && ldsf(smap, i + w) > vj) pk = false;
-                if (x > 0 && ldsf(smap, i - 1) > vj) pk = false;
-                if (x < w - 1 && ldsf(smap, i + 1) > vj) pk = false;
-                if (nms_mode != 0) {
-                    if (y > 0 && x > 0 && ldsf(smap, i - w - 1) > vj) pk = false;
-                    if (y > 0 && x < w - 1 && ldsf(smap, i - w + 1) > vj) pk = false;
-                    if (y < h - 1 && x > 0 && ldsf(smap, i + w - 1) > vj) pk = false;
-                    if (y < h - 1 && x < w - 1 && ldsf(smap, i + w + 1) > vj) pk = false;
-                }
-                if (pk) m |= 1u << j;
-            }
-        }
-        return m;
-    };
-    for (int k = 0; k < nk; k++) {
-        const int v = k * kThreads + threadIdx.x;
-        const unsigned m8 = mask8(v);
-        if (v < nvec) s_m8[v] = (unsigned char)m8;
-    }
-    __syncthreads();
-    // Thread t now owns mask bytes [t*bpt, (t+1)*bpt), i.e. a CONTIGUOUS pixel range, so peak order (np.nonzero:
-    // ascending linear index) is thread order: one block scan of the per-thread counts gives every peak's rank.
-    const int bpt = nk;  // == ceil(nvec / kThreads)
-    const int b0 = threadIdx.x * bpt;
-    int cnt = 0;
-    unsigned long long word = 0;
-    const bool one_word = bpt == 8 && (nvec & 7) == 0;  // the 128 x 128 case: a thread's 64 pixels are one 8-byte LDS read
-                                                       // (only when no thread's range is partial: a ragged tail takes the byte loop)
-    if (one_word) {
-        word = b0 + 8 <= nvec ? *reinterpret_cast<const unsigned long long *>(s_m8 + b0) : 0ull;
-        cnt = __popcll(word);
-    } else {
-        for (int q = b0; q < b0 + bpt && q < nvec; q++) cnt += __popc((unsigned)s_m8[q]);
-    }
-    int incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int n = __shfl_up(incl, d);
-        if (lane >= d) incl += n;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int rank = incl - cnt;
-    for (int q = 0; q < wave; q++) rank += s_wsum[q];
-    int total = 0;
-    for (int q = 0; q < kWaves; q++) total += s_wsum[q];
-    const int kept = total < maxp ? total : maxp;
-    if (one_word) {
-        while (word && rank < maxp) {
-            const int bit = __ffsll((long long)word) - 1;
-            word &= word - 1;
-            s_pk[rank++] = (b0 << 3) + bit;
-        }
-    } else {
-        for (int q = b0; q < b0 + bpt && q < nvec && rank < maxp; q++) {
-            unsigned m = s_m8[q];
-            while (m && rank < maxp) {
-                const int j = __ffs(m) - 1;
-                m &= m - 1;
-                s_pk[rank++] = (q << 3) + j;
-            }
-        }
-    }
-    __syncthreads();
-    stamp(stamps, wg, 2);
-
-    // ---- A4: per-peak refinement, one wave per peak
-    float4 *out = peaks + ((size_t)img * PP_NUM_PART + part) * maxp;
-    for (int p = wave; p < kept; p += kWaves) {
-        const int i = s_pk[p];
-        const int py = i / w, px = i - py * w;
-        float ox, oy, score;
-        if (refine == 2) {
-            // util.refine_centroid (utils/util.py:188-213), radius 2: border peaks are returned unrefined with the raw
-            // score; otherwise offset = sum(box * grid) / sum(box) and score = mean(box).  np.mgrid makes x_grid vary
-            // along ROWS, so the reference's "offset_x" is the row centroid; restated as written.  Sums in f64.
-            if (py - 2 < 0 || py + 3 > h || px - 2 < 0 || px + 3 > w) {
-                ox = (float)px;
-                oy = (float)py;
-                score = ldsf(smap, i);
-            } else {
-                double sx = 0.0, sy = 0.0, sv = 0.0;
-                if (lane < 25) {
-                    const int r = lane / 5, c = lane - r * 5;
-                    const double v = (double)ldsf(smap, (py - 2 + r) * w + (px - 2 + c));
-                    sx = v * (double)(r - 2);
-                    sy = v * (double)(c - 2);
-                    sv = v;
-                }
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    sx += __shfl_xor(sx, d);
-                    sy += __shfl_xor(sy, d);
-                    sv += __shfl_xor(sv, d);
-                }
-                ox = (float)((double)px + sx / sv);
-                oy = (float)((double)py + sy / sv);
-                score = (float)(sv / 25.0);
-            }
-        } else if (refine == 3) {
-            ox = (float)px;
-            oy = (float)py;
-            score = ldsf(smap, i);
-        } else if (refine == 1) {
-            const int x_min = px - 2 < 0 ? 0 : px - 2, y_min = py - 2 < 0 ? 0 : py - 2;  // win_size 2, :135,:143-144
-            const int x_max = px + 2 > w - 1 ? w - 1 : px + 2, y_max = py + 2 > h - 1 ? h - 1 : py + 2;
-            const int pw = x_max - x_min + 1, ph = y_max - y_min + 1;
-            const int uw = pw * 4, n = uw * ph * 4;
-            // separable evaluation, same arithmetic as the per-pixel form: the horizontal pass of every patch row
-            // is computed once (ph x uw values, kept in this wave's LDS scratch), the vertical pass reads 4 of them
-            float *hp = s_hpass[wave];
-            for (int k = lane; k < ph * uw; k += 64) {
-                const int j = k / uw, col = k - j * uw;
-                const int sx = ((col + 2) >> 2) - 1;
-                const float4 ca = reinterpret_cast<const float4 *>(s_cub)[col & 3];
-                const T *row = smap + (y_min + j) * w + x_min;
-                float v = __fmul_rn(ldsf(row, clampi(sx - 1, 0, pw - 1)), ca.x);
-                v = __fadd_rn(v, __fmul_rn(ldsf(row, clampi(sx, 0, pw - 1)), ca.y));
-                v = __fadd_rn(v, __fmul_rn(ldsf(row, clampi(sx + 1, 0, pw - 1)), ca.z));
-                v = __fadd_rn(v, __fmul_rn(ldsf(row, clampi(sx + 2, 0, pw - 1)), ca.w));
-                hp[k] = v;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // this wave's LDS writes precede its reads below
-            __builtin_amdgcn_wave_barrier();
-            float best_v = -INFINITY;
-            int best_k = 0x7fffffff;
-            for (int k = lane; k < n; k += 64) {
-                const int row = k / uw, col = k - row * uw;
-                const int sy = ((row + 2) >> 2) - 1;
-                const float4 cb = reinterpret_cast<const float4 *>(s_cub)[row & 3];
-                float v = __fmul_rn(hp[clampi(sy - 1, 0, ph - 1) * uw + col], cb.x);
-                v = __fadd_rn(v, __fmul_rn(hp[clampi(sy, 0, ph - 1) * uw + col], cb.y));
-                v = __fadd_rn(v, __fmul_rn(hp[clampi(sy + 1, 0, ph - 1) * uw + col], cb.z));
-                v = __fadd_rn(v, __fmul_rn(hp[clampi(sy + 2, 0, ph - 1) * uw + col], cb.w));
-                if (v > best_v || best_k == 0x7fffffff) {
-                    best_v = v;
-                    best_k = k;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            // arg-max with first-occurrence tie-break (ndarray.argmax, :156)
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const float ov = __shfl_xor(best_v, d);
-                const int ok = __shfl_xor(best_k, d);
-                if (ok != 0x7fffffff && (best_k == 0x7fffffff || ov > best_v || (ov == best_v && ok < best_k))) {
-                    best_v = ov;
-                    best_k = ok;
-                }
-            }
-            const int row = best_k / uw, col = best_k - row * uw;
-            ox = (float)(4 * x_min + col);  // :164-171 collapses to stride*x_min + col (exact integer)
-            oy = (float)(4 * y_min + row);
-            score = best_v;
-        } else {
-            ox = __fadd_rn(__fmul_rn(__fadd_rn((float)px, 0.5f), 4.0f), -0.5f);  // compute_resized_coords, :122-123
-            oy = __fadd_rn(__fmul_rn(__fadd_rn((float)py, 0.5f), 4.0f), -0.5f);
-            score = ldsf(smap, i);
-        }
-        if (lane == 0) out[p] = make_float4(ox, oy, score, 0.0f);
-    }
-    if (threadIdx.x == 0) {
-        // write-through (sc1) so that the sorting workgroup below reads this launch's count; correctness never depends on it
-        __hip_atomic_store(counts + img * PP_NUM_PART + part, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        status[img * kFlagWords + part] = total > maxp ? PP_ST_PEAK_OVERFLOW : 0u;  // plain store, every launch
-    }
-    __syncthreads();
-    stamp(stamps, wg, 3);
-    if (!order) return;
-    // ---- the LAST workgroup of the grid orders the images by estimated matching load (sum over limbs of nA * nB), heaviest
-    // first, for K_B's dispatch.  A stale count can only make the order worse, never wrong: the ranks below always form a
-    // permutation of 0..B-1 (ties broken by index) because they are computed from ONE consistent copy in LDS.
-    __shared__ int s_sorter;
-    if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = __hip_atomic_fetch_add(arrive_all, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == (int)(gridDim.x * gridDim.y) - 1;
-        if (last) __hip_atomic_store(arrive_all, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
-        s_sorter = last;
-    }
-    __syncthreads();
-    if (!s_sorter) return;
-    const int B = gridDim.y;
-    int *s_w = reinterpret_cast<int *>(lds_raw);  // the map is no longer needed (the host checked that B ints fit)
-    for (int i = threadIdx.x; i < B; i += kThreads) {
-        int c[PP_NUM_PART];
-#pragma unroll
-        for (int p = 0; p < PP_NUM_PART; p++) {
-            const int v = __hip_atomic_load(counts + i * PP_NUM_PART + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            c[p] = v < maxp ? v : maxp;
-        }
-        int wsum = 0;
-#pragma unroll
-        for (int l = 0; l < PP_NUM_LIMB; l++) wsum += c[kLimbA[l]] * c[kLimbB[l]];
-        s_w[i] = wsum;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < B; i += kThreads) {
-        const int wi = s_w[i];
-        int rank = 0;
-        for (int j = 0; j < B; j++) {
-            const int wj = s_w[j];
-            rank += (wj > wi) || (wj == wi && j < i);
-        }
-        order[rank] = i;
-    }
-}
+#define PP_INC_KA
+#include "posepaf_map_kernels.inc"
+#undef PP_INC_KA
 
 // ------------------------------------------------------------------------------------------------ K_B
 // LDS row stride of K_B's limb map: the row length plus 16 bytes.  Lanes of a wave gather along near-vertical limbs (torso,
@@ -1938,107 +1637,52 @@ __global__ __launch_bounds__(64, 3) void k_assemble_wave(int maxp, const float4 
 // workgroup barrier, one relaxed agent-scope ticket on arrive[img]); the workgroup that draws the last of
 // the 30 tickets re-arms the counter for the next launch, acquires, and its wave 0 assembles the image while the other
 // waves leave.  No workgroup ever waits for another one, so dispatch order and residency cannot deadlock it.
-template <typename T, int NT>
-__global__ __launch_bounds__(NT, NT == 256 ? 3 : 4) void k_limb_connect(const T *__restrict__ net, int n_samples, int h, int w,
-                                                           int flip, int maxp, int cap, int min_img_size,
-                                                           const int *__restrict__ min_img_size_dev,
-                                                           const float4 *__restrict__ peaks,
-                                                           const int *__restrict__ counts, float4 *conns, float4 *aux,
-                                                           int *conn_counts, unsigned *status, const int *__restrict__ order,
-                                                           int *arrive, unsigned *ready, pp_record *records) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    __shared__ int s_poff[PP_NUM_PART];
-    const int limb = blockIdx.x, img = order ? order[blockIdx.y] : blockIdx.y;
-    // Fused form (arrive != NULL): grid (31, B).  Workgroups 0..29 of an image match one limb each and PUBLISH it; workgroup 30
-    // is the image's ASSEMBLY: one wave that consumes limb 0, 1, ... as each is published (the assembly needs them in this
-    // order anyway, pafprocess.cpp:133), so it runs under the matching instead of after it.  arrive[img] is the image's
-    // launch counter (touched by this kernel only): every workgroup of the image reads it at its start, limb l publishes
-    // ready[img][l] = (counter + 1) << 8 | connection count, the assembly stores counter + 1 when it is done -- no flag is
-    // ever reset and a flag of an earlier launch can never be mistaken for this launch's.  The assembly workgroup has the
-    // HIGHEST index of its image: a workgroup is dispatched after every workgroup with a lower index of its XCD's queue, and
-    // limb workgroups never wait, so everything it waits for is running or done (its polling is bounded nevertheless).
-    const unsigned want = arrive ? (((unsigned)arrive[img] + 1u) & 0xffffffu) : 0u;
-    if (limb == PP_NUM_LIMB) {
-        if (threadIdx.x >= 64) return;
-        __builtin_amdgcn_s_setprio(3);   // a lone latency-bound instruction stream next to streaming waves
-        assemble_image_wave<true>(img, threadIdx.x, maxp, peaks + (size_t)img * PP_NUM_PART * maxp, counts + img * PP_NUM_PART,
-                                  conns + (size_t)img * PP_NUM_LIMB * maxp, aux + (size_t)img * PP_NUM_LIMB * maxp,
-                                  conn_counts + img * PP_NUM_LIMB, status, records + img, lds_raw,
-                                  d_stamps ? d_stamps + (size_t)gridDim.x * gridDim.y * 8 : nullptr,  // diagnostics: after the limbs'
-                                  ready + (size_t)img * PP_NUM_LIMB, want);
-        if (threadIdx.x == 0) store_sc1(arrive + img, (int)want);
-        return;
+#define PP_INC_KB
+#include "posepaf_map_kernels.inc"
+#undef PP_INC_KB
+
+// ------------------------------------------------------------------------------------------------ maps larger than LDS
+// The map stays in device memory: k_flip_average_maps writes the 48 used channels, flip-averaged, into a workspace, and K_A / K_B
+// are compiled once more from posepaf_map_kernels.inc with the map pointer aimed at it (no tiling, no new arithmetic).
+constexpr int kWsChannels = PP_NUM_LIMB + PP_NUM_PART;   // [0, 30) limbs, [30, 48) parts: the network's channel order
+template <typename T>
+struct GlobalBicubicSampler {  // maps larger than LDS: the same evaluation on the flip-averaged plane in global memory (dense rows)
+    const T *map;
+    const float *s_cub;
+    int h, w;
+    __device__ __forceinline__ float at(int X, int Y) const {
+        X = clampi(X, 0, 4 * w - 1);  // same clamps as LdsBicubicSampler::at; bicubic4_at clamps its sixteen taps to [0, w) x [0, h)
+        Y = clampi(Y, 0, 4 * h - 1);
+        return bicubic4_at(map, w, 0, 0, w, h, X, Y, s_cub);
     }
-    const int pa = d_limb_pairs[limb][0], pb = d_limb_pairs[limb][1];
-    int nA = counts[img * PP_NUM_PART + pa], nB = counts[img * PP_NUM_PART + pb];
-    nA = nA < maxp ? nA : maxp;
-    nB = nB < maxp ? nB : maxp;
-    int *cc = conn_counts + img * PP_NUM_LIMB + limb;
-    long long *stamps = d_stamps;
-    int ncn_out = 0;
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-    if (nA == 0 || nB == 0) {  // no candidate pairs: no connections (pafprocess.cpp:56-58, :111)
-        if (threadIdx.x == 0) {
-            store_sc1(cc, 0);
-            store_sc1(status + img * kFlagWords + PP_NUM_PART + limb, 0u);
-        }
-    } else {
-        const int ld = limb_map_ld<T>(w);   // padded LDS rows (see load_channel)
-        size_t off = 0;
-        T *smap = reinterpret_cast<T *>(lds_raw);
-        off += (sizeof(T) * (size_t)h * ld + 15) & ~(size_t)15;
-        float *s_cub = reinterpret_cast<float *>(lds_raw + off);
-        off += 64;
-        LimbLds L = carve_limb_lds(lds_raw + off, maxp, cap);
-
-        if (threadIdx.x < 16) s_cub[threadIdx.x] = d_cubic4[threadIdx.x >> 2][threadIdx.x & 3];
-        if (threadIdx.x < 64) {  // flat peak id of each part's first peak (pafprocess.cpp:43-48)
-            int c = threadIdx.x < PP_NUM_PART ? counts[img * PP_NUM_PART + threadIdx.x] : 0;
-            c = c < maxp ? c : maxp;
-            int inc = c;
-#pragma unroll
-            for (int d = 1; d < 32; d <<= 1) {
-                const int t = __shfl_up(inc, d);
-                if ((int)threadIdx.x >= d) inc += t;
-            }
-            if (threadIdx.x < PP_NUM_PART) s_poff[threadIdx.x] = inc - c;
-        }
-        const float4 *pka = peaks + ((size_t)img * PP_NUM_PART + pa) * maxp;
-        const float4 *pkb = peaks + ((size_t)img * PP_NUM_PART + pb) * maxp;
-        for (int i = threadIdx.x; i < nA; i += NT) {
-            const float4 p = pka[i];
-            L.ax[i] = (int)p.x;  // Peak.x/y are ints: truncation (pafprocess.cpp:35-36)
-            L.ay[i] = (int)p.y;
-            L.as[i] = p.z;
-        }
-        for (int i = threadIdx.x; i < nB; i += NT) {
-            const float4 p = pkb[i];
-            L.bx[i] = (int)p.x;
-            L.by[i] = (int)p.y;
-            L.bs[i] = p.z;
-        }
-        const size_t plane = (size_t)h * w;
-        const T *o0 = net + ((size_t)img * n_samples * PP_NUM_CH + limb) * plane;
-        const T *o1 = net + (((size_t)img * n_samples + 1) * PP_NUM_CH + d_flip_paf_ord[limb]) * plane;
-        stamp(stamps, wg, 0);
-        load_channel<NT>(smap, o0, o1, h, w, flip != 0, ld);
-        __syncthreads();
-        stamp(stamps, wg, 1);
-
-        LdsBicubicSampler<T> smp{smap, s_cub, h, w, ld};
-        const int mis = min_img_size_dev ? min_img_size_dev[img] : min_img_size;
-        const size_t row = ((size_t)img * PP_NUM_LIMB + limb) * maxp;
-        ncn_out = connect_limb<LdsBicubicSampler<T>, NT>(smp, L, nA, nB, cap, maxp, mis, conns + row, cc, status + img * kFlagWords + PP_NUM_PART + limb, stamps, wg,
-                     aux + row, s_poff[pa], s_poff[pb]);
-    }
-    if (!arrive) return;  // two-kernel form (timing / diagnostics): k_assemble_wave follows as its own launch
-
-    // ---- publish this limb.  Everything the assembly reads from this workgroup was stored write-through (store_sc1), so there
-    // is no release fence: EVERY storing wave drains its stores, the workgroup meets at a barrier, one lane stores the flag.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) store_sc1(ready + (size_t)img * PP_NUM_LIMB + limb, (want << 8) | (unsigned)ncn_out);
+};
+// The pre-pass of the two kernels below: the 48 channels the post-processing reads, flip-averaged by load_channel itself
+// (so the values are the ones it puts into LDS, binary16 add and halve included) into ws[B][kWsChannels][ws_stride], dense
+// rows.  Grid (48, B).  flip == 0: a plain copy, so the _hbm kernels see one layout.  Reads: load_channel takes its 16-byte
+// vector path only when the row width is a multiple of the vector AND both source planes are 16-byte aligned (a plane of the
+// caller's tensor is not when h*w is odd), reading h*w/8 (h*w/4) whole vectors of the plane; otherwise one element at a time,
+// i < h*w.  Writes: the destination plane starts on a 16-byte boundary (ws_stride) and takes exactly h*w elements.
+constexpr int kMapsThreads = 1024;   // a load_channel instance of its own: the 256- and 512-thread ones stay K_A's and K_B's
+template <typename T>
+__global__ __launch_bounds__(kMapsThreads) void k_flip_average_maps(const T *__restrict__ net, int n_samples, int h, int w, int flip,
+                                                                T *__restrict__ ws, size_t ws_stride) {
+    const int c = blockIdx.x, img = blockIdx.y;
+    const size_t plane = (size_t)h * w;
+    // workspace channel c is network channel c (limbs, then parts); its mirrored partner comes from the d_flip_*_ord tables
+    const int mir = c < PP_NUM_LIMB ? d_flip_paf_ord[c] : PP_NUM_LIMB + d_flip_heat_ord[c - PP_NUM_LIMB];
+    const T *o0 = net + ((size_t)img * n_samples * PP_NUM_CH + c) * plane;
+    const T *o1 = net + (((size_t)img * n_samples + 1) * PP_NUM_CH + mir) * plane;
+    load_channel<kMapsThreads>(ws + ((size_t)img * kWsChannels + c) * ws_stride, o0, o1, h, w, flip != 0);
 }
+
+#define PP_MAPS_HBM
+#define PP_INC_KA
+#include "posepaf_map_kernels.inc"
+#undef PP_INC_KA
+#define PP_INC_KB
+#include "posepaf_map_kernels.inc"
+#undef PP_INC_KB
+#undef PP_MAPS_HBM
 
 // Drop-in path: the caller's (H, W, C) up-sampled map lives in global memory (uploaded by process_paf)
 __global__ __launch_bounds__(kThreads) void k_limb_connect_hwc(const float *__restrict__ paf, int H, int W, int C,
@@ -3218,6 +2862,19 @@ size_t lds_bytes_limb(int elem, int h, int w, int maxp, int cap) {
     const size_t tail = assemble_wave_lds_bytes(maxp);  // the last limb workgroup of an image assembles it in the same region
     return limb > tail ? limb : tail;
 }
+// the _hbm instances: no map in LDS; K_A ends with the image sorter's `batch` ints, K_B shares its region with the assembly tail
+size_t lds_bytes_heat_hbm(int h, int w, int maxp, int batch) {
+    const size_t npix = (size_t)h * w;
+    return 64 + ((4 * (size_t)maxp + 15) & ~(size_t)15) + ((npix + 7) / 8 + 15) / 16 * 16 + ((4 * (size_t)batch + 15) & ~(size_t)15);
+}
+size_t lds_bytes_limb_hbm(int maxp, int cap) {
+    const size_t limb = 64 + limb_lds_bytes(maxp, cap), tail = assemble_wave_lds_bytes(maxp);
+    return limb > tail ? limb : tail;
+}
+size_t map_plane_stride(int elem, int h, int w) { return (((size_t)h * w * elem + 15) & ~(size_t)15) / elem; }
+size_t map_workspace_bytes(int batch, int h, int w) {   // sized for fp32, 16 bytes of slack at the very end
+    return (size_t)batch * kWsChannels * map_plane_stride(4, h, w) * 4 + 16;
+}
 size_t lds_bytes_limb_hwc(int maxp, int cap) { return limb_lds_bytes(maxp, cap); }
 size_t lds_bytes_assemble(int maxp) { return assemble_lds_bytes(maxp); }
 
@@ -3245,6 +2902,12 @@ hipError_t init_kernel_attributes() {
                          reinterpret_cast<const void *>(&k_limb_connect<float, 256>),
                          reinterpret_cast<const void *>(&k_limb_connect<__half, 512>),
                          reinterpret_cast<const void *>(&k_limb_connect<float, 512>),
+                         reinterpret_cast<const void *>(&k_heat_peaks_hbm<__half>),
+                         reinterpret_cast<const void *>(&k_heat_peaks_hbm<float>),
+                         reinterpret_cast<const void *>(&k_limb_connect_hbm<__half, 256>),
+                         reinterpret_cast<const void *>(&k_limb_connect_hbm<float, 256>),
+                         reinterpret_cast<const void *>(&k_limb_connect_hbm<__half, 512>),
+                         reinterpret_cast<const void *>(&k_limb_connect_hbm<float, 512>),
                          reinterpret_cast<const void *>(&k_limb_connect_hwc),
                          reinterpret_cast<const void *>(&k_assemble),
                          reinterpret_cast<const void *>(&k_assemble_wave),
@@ -3305,6 +2968,54 @@ hipError_t launch_limb_connect(const void *net, int dtype, int batch, int n_samp
 #define PP_LAUNCH_LIMB(T, NT)                                                                                                   \
     hipLaunchKernelGGL((k_limb_connect<T, NT>), grid, block, lds, stream, static_cast<const T *>(net), n_samples, h, w, flip, maxp, \
                        cap, min_img_size, min_img_size_dev, peaks, counts, conns, aux, conn_counts, status, order, arrive, ready, records)
+    if (dtype == PP_F16) {
+        if (nt == 512) PP_LAUNCH_LIMB(__half, 512);
+        else PP_LAUNCH_LIMB(__half, 256);
+    } else {
+        if (nt == 512) PP_LAUNCH_LIMB(float, 512);
+        else PP_LAUNCH_LIMB(float, 256);
+    }
+#undef PP_LAUNCH_LIMB
+    return hipGetLastError();
+}
+
+// ---- maps larger than LDS: pre-pass + the _hbm instances (ws: map_workspace_bytes, planes of map_plane_stride elements)
+hipError_t launch_flip_average_maps(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, void *ws,
+                                    hipStream_t stream) {
+    const dim3 grid(kWsChannels, batch), block(kMapsThreads);
+    if (dtype == PP_F16)
+        hipLaunchKernelGGL(k_flip_average_maps<__half>, grid, block, 0, stream, static_cast<const __half *>(net), n_samples, h, w,
+                           flip, static_cast<__half *>(ws), map_plane_stride(2, h, w));
+    else
+        hipLaunchKernelGGL(k_flip_average_maps<float>, grid, block, 0, stream, static_cast<const float *>(net), n_samples, h, w,
+                           flip, static_cast<float *>(ws), map_plane_stride(4, h, w));
+    return hipGetLastError();
+}
+
+hipError_t launch_heat_peaks_hbm(const void *ws, int dtype, int batch, int h, int w, int refine, int nms_mode, float thr, int maxp,
+                                 float4 *peaks, int *counts, unsigned *status, int *order, int *arrive_all, hipStream_t stream) {
+    const dim3 grid(PP_NUM_PART, batch), block(kThreads);
+    const size_t lds = lds_bytes_heat_hbm(h, w, maxp, batch);
+    if (dtype == PP_F16)
+        hipLaunchKernelGGL(k_heat_peaks_hbm<__half>, grid, block, lds, stream, static_cast<const __half *>(ws),
+                           map_plane_stride(2, h, w), h, w, refine, nms_mode, thr, maxp, peaks, counts, status, order, arrive_all);
+    else
+        hipLaunchKernelGGL(k_heat_peaks_hbm<float>, grid, block, lds, stream, static_cast<const float *>(ws),
+                           map_plane_stride(4, h, w), h, w, refine, nms_mode, thr, maxp, peaks, counts, status, order, arrive_all);
+    return hipGetLastError();
+}
+
+hipError_t launch_limb_connect_hbm(const void *ws, int dtype, int batch, int h, int w, int maxp, int cap, int min_img_size,
+                                   const int *min_img_size_dev, const float4 *peaks, const int *counts, float4 *conns, float4 *aux,
+                                   int *conn_counts, unsigned *status, const int *order, int *arrive, unsigned *ready,
+                                   pp_record *records, hipStream_t stream) {
+    const int nt = limb_threads();
+    const dim3 grid(PP_NUM_LIMB + (arrive ? 1 : 0), batch), block(nt);
+    const size_t lds = lds_bytes_limb_hbm(maxp, cap);
+#define PP_LAUNCH_LIMB(T, NT)                                                                                                       \
+    hipLaunchKernelGGL((k_limb_connect_hbm<T, NT>), grid, block, lds, stream, static_cast<const T *>(ws),                            \
+                       map_plane_stride(sizeof(T), h, w), h, w, maxp, cap, min_img_size, min_img_size_dev, peaks, counts, conns, aux, \
+                       conn_counts, status, order, arrive, ready, records)
     if (dtype == PP_F16) {
         if (nt == 512) PP_LAUNCH_LIMB(__half, 512);
         else PP_LAUNCH_LIMB(__half, 256);

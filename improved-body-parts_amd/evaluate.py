@@ -317,8 +317,13 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
     eng.sync()
     dt = time.perf_counter() - t0
     feeder.close()
-    return local.view(-1), dt, {"plans": sorted(eng.plans), "decode_threads": workers,
-                                "conv_table": fused_model.table_hash(), "launch": "eager" if a.no_graph else "hipGraph replay"}
+    info = {"plans": sorted(eng.plans), "decode_threads": workers,
+            "conv_table": fused_model.table_hash(), "launch": "eager" if a.no_graph else "hipGraph replay"}
+    if a.run_cpp:   # where pp_process_batch kept the maps it was handed (dtype and shape of each bucket's network output)
+        kinds = {post.map_residency(p.maps.dtype, p.maps.shape[3], p.maps.shape[4]) for p in eng.plans.values() if p.maps is not None}
+        if kinds:
+            info["map_residency"] = kinds.pop() if len(kinds) == 1 else "mixed"
+    return local.view(-1), dt, info
 
 
 def run_original(a, src, mine, model, post, dev):
@@ -504,7 +509,8 @@ def main(argv=None):
     all_shapes = [src.shape(int(i)) for i in (range(n_images) if n_images <= 200_000 else mine)]
     hp = max(padded_shape(h, w)[0] for h, w in all_shapes) // 4
     wp = max(padded_shape(h, w)[1] for h, w in all_shapes) // 4
-    # feature maps up to hp x wp (area bound; pp_process_batch refuses a map that does not fit LDS, loudly)
+    # feature maps up to hp x wp (area bound).  With the C++ rules a map that does not fit LDS stays in device memory (the
+    # large-map kernels, up to 650 x 950); the Python rules refuse such a map, loudly
     post = PosePostProcessor(max_batch=a.batch, max_h=hp if not original else int(hp * max(scales) + 16),
                              max_w=wp if not original else int(wp * max(scales) + 16), max_peaks_per_part=64, device=local)
     if original:

@@ -17,6 +17,7 @@ PP_F32, PP_F16 = 0, 1
 ST_PEAK_OVERFLOW, ST_HUMAN_OVERFLOW, ST_SKEL_OVERFLOW, ST_SORT_UNDEFINED, ST_CAND_OVERFLOW, ST_FLOAT_COORDS = 1, 2, 4, 8, 16, 32
 ST_SYNC_TIMEOUT = 64
 ST_RECON_UNDEFINED = 128          # remove_recon = 1: the reference raises on a connection of this image (nothing changed)
+PP_MAPS_AUTO, PP_MAPS_LDS, PP_MAPS_HBM = 0, 1, 2   # pp_map_residency_mode (include/posepaf.h)
 ST_DEFINED_MASK = 0xFF            # include/posepaf.h:53-61; any other bit in pp_record.status is corruption
 ST_OVERFLOW_MASK = ST_PEAK_OVERFLOW | ST_HUMAN_OVERFLOW | ST_SKEL_OVERFLOW | ST_CAND_OVERFLOW
 
@@ -34,6 +35,7 @@ EXPORTS = [
     "pp_get_part_score", "pp_get_status", "pp_py_find_connections_host", "pp_py_find_humans_host", "pp_original_accumulate", "pp_original_accumulate_all", "pp_original_finish",
     "pp_preprocess_u8_affine", "pp_original_accumulate_affine", "pp_original_accumulate_all_affine", "pp_warp_affine_f32",
     "pp_resize_u8_cubic", "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
+    "pp_set_map_residency", "pp_map_residency", "pp_map_workspace_bytes", "pp_time_map_prepass",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -87,6 +89,11 @@ def load():
     L.pp_nms_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_nms_batch_ex.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.pp_time_kernels.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp]
+    L.pp_time_map_prepass.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp]
+    L.pp_set_map_residency.argtypes = [vp, C.c_int]
+    L.pp_map_residency.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.pp_map_workspace_bytes.argtypes = [vp]
+    L.pp_map_workspace_bytes.restype = C.c_longlong
     L.pp_bias_act_f16.argtypes = [vp, vp, vp, vp, C.c_long, C.c_int, C.c_float, C.c_int, vp]
     L.pp_maxpool2_f16.argtypes = [vp, vp, C.c_long, C.c_int, C.c_int, C.c_int, vp]
     L.pp_upsample2_f16.argtypes = [vp, vp, C.c_long, C.c_int, C.c_int, C.c_int, vp]

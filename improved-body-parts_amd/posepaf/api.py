@@ -4,6 +4,7 @@ torch is used for device memory and streams only; every number comes out of the 
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -27,6 +28,37 @@ class PosePostProcessor:
         self.device = device
         self.max_batch, self.maxp = max_batch, max_peaks_per_part
         self._records = torch.empty(max_batch * RECORD_BYTES, dtype=torch.uint8, device=f"cuda:{device}")
+        if os.environ.get("POSEPAF_MAPS", "").lower() == "hbm":   # A/B runs: every shape takes the large-map kernels
+            self.set_map_residency("hbm")
+
+    def set_map_residency(self, mode):
+        """pp_set_map_residency: "auto" (a map that fits LDS is staged there, a larger one stays in device memory) or "hbm"
+        (every shape takes the large-map path: the pre-pass and the _hbm kernels).  Not to be called under graph capture."""
+        codes = {"auto": _lib.PP_MAPS_AUTO, "hbm": _lib.PP_MAPS_HBM, _lib.PP_MAPS_AUTO: _lib.PP_MAPS_AUTO,
+                 _lib.PP_MAPS_HBM: _lib.PP_MAPS_HBM}
+        if mode not in codes:
+            raise PosePafError(f"map residency must be 'auto' or 'hbm', got {mode!r}")
+        _lib.check(self.L.pp_set_map_residency(self.ctx, codes[mode]), self.ctx)
+
+    def map_residency(self, dtype, h: int, w: int) -> str:
+        """pp_map_residency: "lds" or "hbm" for a (h, w) map of `dtype` (torch / numpy float16 or float32, or PP_F16 / PP_F32);
+        raises PosePafError (PP_ERR_TOO_LARGE) for a shape the context cannot take."""
+        if isinstance(dtype, int) and dtype in (PP_F16, PP_F32):
+            code = dtype
+        else:
+            name = str(dtype).replace("<class '", "").replace("'>", "").split(".")[-1]   # torch.float16 / np.float16 / np.dtype -> "float16"
+            if name not in ("float16", "float32"):
+                raise PosePafError(f"map dtype must be float16 or float32, got {dtype}")
+            code = PP_F16 if name == "float16" else PP_F32
+        rc = self.L.pp_map_residency(self.ctx, code, int(h), int(w))
+        if rc < 0:
+            _lib.check(rc, self.ctx)
+        return "hbm" if rc == _lib.PP_MAPS_HBM else "lds"
+
+    @property
+    def map_workspace_bytes(self) -> int:
+        """Bytes of the large-map workspace this context holds (0: none allocated)."""
+        return int(self.L.pp_map_workspace_bytes(self.ctx))
 
     def close(self):
         if getattr(self, "ctx", None) is not None and self.ctx.value:
@@ -118,6 +150,17 @@ class PosePostProcessor:
         _lib.check(self.L.pp_time_kernels(self.ctx, B, C.c_void_p(net_out.data_ptr()), self._dtype_code(net_out), h, w,
                                           int(flip), int(min_img_size), int(iters), ms, C.c_void_p(stream)), self.ctx)
         return {"k_heat_peaks": ms[0], "k_limb_connect": ms[1], "k_assemble_wave": ms[2], "chain": ms[3]}
+
+    def time_map_prepass(self, net_out, flip: bool = True, iters: int = 20) -> float:
+        """HIP-event timing of k_flip_average_maps, the pre-pass of a map kept in device memory: ms per launch (0.0 when the
+        shape is staged in LDS and has no pre-pass)."""
+        import torch
+        B, h, w = self._check_input(net_out, flip)
+        ms = C.c_float(0.0)
+        stream = torch.cuda.current_stream(net_out.device).cuda_stream
+        _lib.check(self.L.pp_time_map_prepass(self.ctx, B, C.c_void_p(net_out.data_ptr()), self._dtype_code(net_out), h, w,
+                                              int(flip), int(iters), C.byref(ms), C.c_void_p(stream)), self.ctx)
+        return float(ms.value)
 
     def set_test_cfg(self, cfg=None):
         """pp_set_test_cfg: the run-time values of the Python rules (thre2, connect_ration, mid_num, len_rate, connection_tole,

@@ -41,7 +41,8 @@ typedef enum {
     PP_OK = 0,
     PP_ERR_NO_DEVICE = -1,   /* no HIP device / runtime error at create */
     PP_ERR_BAD_ARG = -2,
-    PP_ERR_TOO_LARGE = -3,   /* batch/h/w beyond what the context was created for, or map does not fit LDS */
+    PP_ERR_TOO_LARGE = -3,   /* batch/h/w beyond what the context was created for; a map above 650x950; on the Python-rule
+                                path (pp_process_batch_py) also a map that does not fit LDS */
     PP_ERR_HIP = -4,         /* a HIP call failed; pp_last_hip_error() has the code */
     PP_ERR_OVERFLOW = -5,    /* compat path only: a per-part / per-image capacity was exceeded */
     PP_ERR_UNSUPPORTED = -6  /* pp_conv_f16: this tile configuration / channel count is not available for the shape */
@@ -108,11 +109,28 @@ PP_API int pp_device_available(void);
 PP_API int pp_process_batch(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip,
                      int min_img_size, const int *min_img_size_dev, pp_record *records_dev, void *stream);
 
+/* Where the kernels of pp_process_batch / pp_nms_batch / pp_nms_batch_ex / pp_time_kernels keep a feature map while they
+ * work on it.  A channel that fits LDS (up to roughly 270x270 binary16, 190x190 float32) is staged there by each workgroup:
+ * two launches.  A larger one -- up to 650x950, the reference's own cap (utils/parse_skeletons.py:46-49) -- stays in device
+ * memory: a pre-pass writes the 48 flip-averaged channels into a workspace of the context and the same two kernels read it
+ * through a global pointer (three launches, same results bit for bit, still nothing allocated or synchronised per call).
+ * pp_create allocates that workspace (max_batch * 48 * plane * 4 bytes) only when a float32 max_h x max_w map would not fit LDS.
+ * pp_set_map_residency(PP_MAPS_HBM) sends EVERY shape down the large-map path (A/B measurements, tests at small shapes) and
+ * allocates the workspace if pp_create did not; PP_MAPS_AUTO restores the default.  A setter: never call it under stream capture.
+ * pp_map_residency: PP_MAPS_LDS or PP_MAPS_HBM for the shape as pp_process_batch would run it, or PP_ERR_TOO_LARGE.
+ * pp_map_workspace_bytes: size of the workspace (0: none allocated).
+ * pp_process_batch_py (the Python rules) has no large-map kernels yet and keeps answering PP_ERR_TOO_LARGE beyond LDS. */
+typedef enum { PP_MAPS_AUTO = 0, PP_MAPS_LDS = 1, PP_MAPS_HBM = 2 } pp_map_residency_mode;
+PP_API int pp_set_map_residency(pp_ctx *ctx, int mode);
+PP_API int pp_map_residency(const pp_ctx *ctx, int dtype, int h, int w);
+PP_API long long pp_map_workspace_bytes(const pp_ctx *ctx);
+
 /* The same batched path with the rules of the reference's PURE-PYTHON matching, find_connections + find_humans
  * (utils/parse_skeletons.py:324-600) -- what evaluate.py runs with --run_refactor but WITHOUT --run_cpp.  It differs
  * from the C++ rules in sampling (np.round(np.linspace)), float64 arithmetic, a stable sort, the merge conditions and the
  * score bookkeeping.  img_height is find_connections' `img_height` argument.  Thresholds are the
- * INI defaults (utils/config:17-25).  Needs max_peaks_per_part <= 64. */
+ * INI defaults (utils/config:17-25).  Needs max_peaks_per_part <= 64.
+ * The map must fit LDS (PP_ERR_TOO_LARGE otherwise): the large-map kernels exist for the C++ rules only. */
 PP_API int pp_process_batch_py(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip,
                                int img_height, const int *img_height_dev, pp_record *records_dev, void *stream);
 
@@ -139,9 +157,13 @@ PP_API int pp_nms_batch_ex(pp_ctx *ctx, int batch, const void *net_out_dev, int 
  * ms_out[0] = k_heat_peaks (peaks + the image ordering), ms_out[1] = k_limb_connect (limb scoring, matching AND the
  * person assembly done by each image's last limb workgroup), ms_out[2] = k_assemble_wave (the assembly alone as its own
  * one-wave-per-image launch; diagnostic, not part of the chain), ms_out[3] = the whole chain as pp_process_batch enqueues it.
- * ms_out must hold 4 floats.  Blocking. */
+ * ms_out must hold 4 floats.  Blocking.  For a map kept in device memory (pp_map_residency) [0] and [1] are the _hbm instances
+ * and [3] includes the pre-pass; pp_time_map_prepass times that pre-pass (k_flip_average_maps) alone the same way, *ms_out = 0
+ * when the shape has none. */
 PP_API int pp_time_kernels(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip,
                            int min_img_size, int iters, float *ms_out, void *stream);
+PP_API int pp_time_map_prepass(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip, int iters,
+                               float *ms_out, void *stream);
 
 /* Forward-pass helpers (not part of the reference's interface), all on channels-last (NHWC) fp16 DEVICE tensors with
  * channels % 8 == 0 and 16-byte aligned pointers:
