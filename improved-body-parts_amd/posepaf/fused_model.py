@@ -37,6 +37,7 @@ USE_FUSED_CONV = True
 USE_OWN_CONV = True
 TUNE_MIOPEN = os.environ.get("POSEPAF_TUNE_MIOPEN", "0") == "1"   # also time MIOpen + epilogue pass where fused kernels exist
 OWN_VARIANTS = {101: 256, 102: 128, 103: 64, 104: 512}
+UP2_COLLAPSED_BN = (256, 128, 64, 512)   # forward_up2's choices 2..5; 512: the halo-tile kernel walking the four taps of each output phase
 PW_VARIANT = 105            # the streaming 1x1 kernel (pp_pw_f16): weights resident in LDS, pixel fragments straight from HBM
 USE_PW = True
 USE_SUM_FUSION = True       # the SE block's channel sums leave the 3x3 kernel that produces the feature map
@@ -77,9 +78,47 @@ def _timed(fn):
     return sorted(ts)[len(ts) // 2]
 
 
+def _capturing() -> bool:
+    """no timing inside a stream capture (it synchronises): shapes are tuned by the eager warm-up pass"""
+    return torch.cuda.is_current_stream_capturing()
+
+
 def _note(key, choice) -> None:
     if _progress is not None:
         _progress(f"tuned shape {len(_conv_choice)}: {key} -> {choice}")
+
+
+def _record(key, choice, times):
+    _conv_choice[key] = choice
+    _conv_timing[key] = times
+    _note(key, choice)
+    return choice
+
+
+def _choose(key, eligible, candidates):
+    """The tuning protocol of the fused forms (up2, dual, mean, pool, cat) -> the choice for the shape `key`.
+    candidates: [(choice value, timing label, thunk), ...] in tuning order, the separate form first; a thunk returns its result,
+    or None when its kernel refuses the shape.  Not eligible: the separate form, nothing looked up or recorded.  A key the table
+    holds: its entry, nothing timed.  A new key inside a capture: the separate form, nothing recorded.  Otherwise the separate
+    form runs once untimed (its inner plain convolutions get their own table entries first), then the candidates that take the
+    shape are timed in order, and a later one replaces the best only when it is strictly faster."""
+    (best, label, separate), fused = candidates[0], candidates[1:]
+    if not eligible:
+        return best
+    choice = _conv_choice.get(key)
+    if choice is not None:
+        return choice
+    if _capturing():
+        return best
+    separate()
+    times = {label: _timed(separate)}
+    best_t = times[label]
+    for value, label, thunk in fused:
+        if thunk() is not None:
+            times[label] = _timed(thunk)
+            if times[label] < best_t:
+                best, best_t = value, times[label]
+    return _record(key, best, times)
 
 
 def conv_choices() -> dict:
@@ -94,7 +133,7 @@ def _key_to_json(k):
 
 
 def _key_from_json(k):
-    return tuple(bool(v[1]) if isinstance(v, list) else v for v in k)
+    return tuple(bool(v[1]) if isinstance(v, (list, tuple)) else v for v in k)   # (a tuple: entries that never went through JSON)
 
 
 def table_entries() -> list:
@@ -336,6 +375,22 @@ class FConv(nn.Module):
     def conv_only(self, x):
         return F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation)
 
+    def _w(self, name="weight"):
+        """the weight tensor in the channels-last layout the kernels read (re-laid in place at first use)"""
+        p = getattr(self, name)
+        if not p.is_contiguous(memory_format=torch.channels_last):
+            p.data = p.data.contiguous(memory_format=torch.channels_last)
+        return p
+
+    @property
+    def _slope(self):
+        return LEAK if self.act else 1.0
+
+    def _out(self, x, h, w, k=None):
+        """an uninitialised channels-last output of x's batch, dtype and device, (h, w) pixels, this layer's channels"""
+        return torch.empty((x.shape[0], k or self.weight.shape[0], h, w), dtype=x.dtype, device=x.device,
+                           memory_format=torch.channels_last)
+
     def _pointwise_ok(self, x):
         if not (USE_PWCONV and x.is_cuda and x.dtype == torch.float16 and self.weight.shape[2:] == (1, 1)
                 and self.stride == (1, 1) and self.padding == (0, 0)):
@@ -357,22 +412,22 @@ class FConv(nn.Module):
         if cfg == 104 and sliced:   # the 3x3 halo kernel takes pixel strides on both sides
             return _lib.load().pp_conv_own_ld_f16(_ptr(x), _ptr(self.weight), _ptr(self.bias), _ptr(extra), _ptr(y), n, h, w, c,
                                                   self.weight.shape[0], self.weight.shape[2], self.padding[0], self.dilation[0], mode,
-                                                  LEAK if self.act else 1.0, 512, x.stride(3), y.stride(3), _stream(x))
+                                                  self._slope, 512, x.stride(3), y.stride(3), _stream(x))
         if cfg >= 100 and (x.stride(3) != c or (cfg != PW_VARIANT and y.stride(3) != self.weight.shape[0])):
             return -6   # the implicit-GEMM kernels read and write packed pixels; the streaming 1x1 kernel writes a channel slice
         if cfg == PW_VARIANT:
             if self.weight.shape[2] != 1 or self.padding[0] != 0:
                 return -6
             return _lib.load().pp_pw_f16(_ptr(x), None, _ptr(self.weight), _ptr(self.bias), _ptr(extra), None, _ptr(y), None,
-                                         n * h * w, h * w, c, self.weight.shape[0], y.stride(3), mode, LEAK if self.act else 1.0,
+                                         n * h * w, h * w, c, self.weight.shape[0], y.stride(3), mode, self._slope,
                                          _stream(x))
         if cfg >= 100:   # hand-written kernels (csrc/posepaf_conv_own.hip): workgroup-tile variant OWN_VARIANTS[cfg]
             return _lib.load().pp_conv_own_f16(_ptr(x), _ptr(self.weight), _ptr(self.bias), _ptr(extra), _ptr(y), n, h, w, c,
                                                self.weight.shape[0], self.weight.shape[2], self.padding[0], self.dilation[0], mode,
-                                               LEAK if self.act else 1.0, OWN_VARIANTS[cfg], _stream(x))
+                                               self._slope, OWN_VARIANTS[cfg], _stream(x))
         return _lib.load().pp_conv_ld_f16(_ptr(x), _ptr(self.weight), _ptr(self.bias), _ptr(extra), _ptr(y), n, h, w, c,
                                           self.weight.shape[0], self.weight.shape[2], self.padding[0], self.dilation[0], mode,
-                                          LEAK if self.act else 1.0, cfg, x.stride(3), y.stride(3), _stream(x))
+                                          self._slope, cfg, x.stride(3), y.stride(3), _stream(x))
 
     def _fused(self, x, res, post, out=None):
         """-> y, or None when this shape runs faster (or only) on the MIOpen + epilogue path.  x may be a channel slice of a wider
@@ -382,8 +437,7 @@ class FConv(nn.Module):
         extra = res if res is not None else post
         extra = _cl(extra) if extra is not None else None
         mode = 1 if res is not None else (2 if post is not None else 0)
-        if not self.weight.is_contiguous(memory_format=torch.channels_last):
-            self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+        self._w()
         n, c, h, w = x.shape
         k, r = self.weight.shape[0], self.weight.shape[2]
         ho = h + 2 * self.padding[0] - self.dilation[0] * (r - 1)
@@ -394,10 +448,10 @@ class FConv(nn.Module):
             key = key + ("slice", x.stride(3), out.stride(3) if out is not None else k)
         choice = _conv_choice.get(key)
         _conv_calls[key] = _conv_calls.get(key, 0) + 1
-        y = out if out is not None else torch.empty((n, k, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        y = out if out is not None else self._out(x, ho, wo)
         if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                return None  # cannot time inside a capture; shapes are tuned by the eager warm-up pass
+            if _capturing():
+                return None
             choice = self._tune(key, x, extra, mode, y, res, post)
         if choice < 0:
             return None
@@ -405,22 +459,9 @@ class FConv(nn.Module):
         return y
 
     def _tune(self, key, x, extra, mode, y, res, post):
+        """The plain convolution's own selection rule: every configuration that takes the shape, library templates first."""
         from . import _lib
         L = _lib.load()
-
-        def timed(fn):   # median of _TUNE_REPS single-launch timings after one warm-up
-            fn()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(_TUNE_REPS):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1))
-            return sorted(ts)[len(ts) // 2]
-
         best, best_t, times = -1, float("inf"), {}
         own = [c_ for c_ in OWN_VARIANTS if USE_OWN_CONV and L.pp_conv_own_supported(x.shape[1], self.weight.shape[0],
                                                                                      self.weight.shape[2])]
@@ -429,7 +470,7 @@ class FConv(nn.Module):
         for cfg in list(range(L.pp_conv_num_configs())) + own:
             if self._fused_launch(cfg, x, extra, mode, y) != 0:
                 continue
-            t = timed(lambda: self._fused_launch(cfg, x, extra, mode, y))
+            t = _timed(lambda: self._fused_launch(cfg, x, extra, mode, y))
             times[cfg] = t
             # (the library templates are timed first; a hand-written kernel within OWN_MARGIN of the best of them takes the shape --
             # the 1x1 shapes sit within +-2 % of each other and would otherwise flip between runs)
@@ -439,14 +480,11 @@ class FConv(nn.Module):
         # kernels exist costs an exhaustive MIOpen find per shape (most of the warm-up) and it never won a shape worth more than
         # 0.06 ms: it is timed only on request (POSEPAF_TUNE_MIOPEN=1) or when nothing else ran.
         if best < 0 or TUNE_MIOPEN:
-            t = timed(lambda: hip_bias_act_(self.conv_only(x), self.bias, res, self.act, post))
+            t = _timed(lambda: hip_bias_act_(self.conv_only(x), self.bias, res, self.act, post))
             times["miopen"] = t
             if t < best_t:
                 best, best_t = -1, t
-        _conv_choice[key] = best
-        _conv_timing[key] = times
-        _note(key, best)
-        return best
+        return _record(key, best, times)
 
     # ---- x2 nearest upsample in front, up to two tensors added behind: one launch of the 3x3 halo kernel (pp_conv_own_ex_f16)
     def _collapsed_weights(self):
@@ -470,79 +508,92 @@ class FConv(nn.Module):
             self._w4 = w4
         return w4
 
+    def _up2_fused(self, low, post, post2):
+        """forward_up2's one-launch forms, where they apply: run(choice) -> y, or None when the kernel refuses the shape"""
+        if not (USE_OWN_CONV and low.is_cuda and low.dtype == torch.float16 and self.stride == (1, 1)
+                and tuple(self.weight.shape[2:]) == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1)):
+            return None
+        from . import _lib
+        n, c, h, w = low.shape
+        k = self.weight.shape[0]
+        mode = 3 if post2 is not None else 2
+
+        def run(choice):
+            bn = UP2_COLLAPSED_BN[choice - 2] if choice >= 2 else 0
+            if bn and (not USE_COLLAPSED_UP2 or k % (bn if bn != 512 else 64)):
+                return None
+            x, y = _cl(low), self._out(low, 2 * h, 2 * w)
+            e1, e2 = _cl(post), (_cl(post2) if post2 is not None else None)
+            if bn:
+                rc = _lib.load().pp_conv_up2_collapsed_f16(_ptr(x), _ptr(self._collapsed_weights()), _ptr(self.bias), _ptr(e1), _ptr(e2),
+                                                           _ptr(y), n, h, w, c, k, mode, self._slope, bn, _stream(x))
+            else:
+                rc = _lib.load().pp_conv_own_ex_f16(_ptr(x), _ptr(self._w()), _ptr(self.bias), _ptr(e1), _ptr(e2), _ptr(y), None, n, 2 * h,
+                                                    2 * w, c, k, 3, 1, 1, mode, self._slope, 512, 1, _stream(x))
+            return y if rc == 0 else None
+        return run
+
     def forward_up2(self, low, post, post2=None):
         """act(conv(upsample2(low)) + bias) + post (+ post2), three ways, the fastest kept per shape (timed once):
         0 separate: upsample2 -> convolution (-> add3);  1 the upsample read through the 3x3 halo kernel's own loads, adds in its
         epilogue (pp_conv_own_ex_f16);  2.. the COLLAPSED form (pp_conv_up2_collapsed_f16): four 2x2 convolutions of the
         half-resolution tensor, 2.25x fewer multiply-adds for the same real-number result (choice = 2 + the tile width index)."""
-        from . import _lib
         n, c, h, w = low.shape
-        k = self.weight.shape[0]
-        key = ("up2", n, c, h, w, k, post2 is not None, bool(self.act))
-        fused_ok = (USE_OWN_CONV and low.is_cuda and low.dtype == torch.float16 and self.stride == (1, 1)
-                    and tuple(self.weight.shape[2:]) == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1))
-        COLLAPSED_BN = (256, 128, 64, 512)   # 512: the halo-tile kernel walking the four taps of each output phase
+        key = ("up2", n, c, h, w, self.weight.shape[0], post2 is not None, bool(self.act))
 
         def separate():
             if post2 is None:
                 return self(upsample2(low), post=post)
             return add3(self(upsample2(low)), post, post2)   # the conv runs without the extra read, ONE pass adds the three
 
-        def fused():
-            x = _cl(low)
-            if not self.weight.is_contiguous(memory_format=torch.channels_last):
-                self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
-            y = torch.empty((n, k, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            e1, e2 = _cl(post), (_cl(post2) if post2 is not None else None)
-            rc = _lib.load().pp_conv_own_ex_f16(_ptr(x), _ptr(self.weight), _ptr(self.bias), _ptr(e1), _ptr(e2), _ptr(y), None, n, 2 * h, 2 * w,
-                                                c, k, 3, 1, 1, 3 if post2 is not None else 2, LEAK if self.act else 1.0, 512, 1, _stream(x))
-            return y if rc == 0 else None
-
-        def collapsed(bn):
-            if not USE_COLLAPSED_UP2 or k % (bn if bn != 512 else 64):
-                return None
-            x = _cl(low)
-            y = torch.empty((n, k, 2 * h, 2 * w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            e1, e2 = _cl(post), (_cl(post2) if post2 is not None else None)
-            rc = _lib.load().pp_conv_up2_collapsed_f16(_ptr(x), _ptr(self._collapsed_weights()), _ptr(self.bias), _ptr(e1), _ptr(e2), _ptr(y),
-                                                       n, h, w, c, k, 3 if post2 is not None else 2, LEAK if self.act else 1.0, bn,
-                                                       _stream(x))
-            return y if rc == 0 else None
-
-        choice = _conv_choice.get(key) if fused_ok else 0
-        if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                return separate()
-            separate()                      # tunes the inner convolution's shape first
-            times = {"separate": _timed(separate)}
-            choice, best = 0, times["separate"]
-            if fused() is not None:
-                times["fused"] = _timed(fused)
-                if times["fused"] < best:
-                    choice, best = 1, times["fused"]
-            for i, bn in enumerate(COLLAPSED_BN):
-                if collapsed(bn) is not None:
-                    times[f"collapsed{bn}"] = _timed(lambda: collapsed(bn))
-                    if times[f"collapsed{bn}"] < best:
-                        choice, best = 2 + i, times[f"collapsed{bn}"]
-            _conv_timing[key] = times
-            _conv_choice[key] = choice
-            _note(key, choice)
-        if choice >= 2:
-            y = collapsed(COLLAPSED_BN[choice - 2])
-            if y is not None:
-                return y
-        elif choice == 1:
-            y = fused()
-            if y is not None:
-                return y
-        return separate()
+        run = self._up2_fused(low, post, post2)
+        choice = _choose(key, run is not None, [(0, "separate", separate), (1, "fused", lambda: run(1))] + [
+            (2 + i, f"collapsed{bn}", lambda i=i: run(2 + i)) for i, bn in enumerate(UP2_COLLAPSED_BN)])
+        y = run(choice) if choice else None
+        return separate() if y is None else y
 
     # ---- two outputs: y = act(conv(x) + bias + res) and y + other, one launch of an own kernel (pp_conv_own_ex_f16 mode 4)
+    def _dual_fused(self, x, scale, res, other, want_pool, pool_ok):
+        """forward_dual's one-launch forms, where they apply: run(tile id) -> (y, y2[, pooled]), or None when the kernel refuses"""
+        from . import _lib
+        n, c, h, w = x.shape
+        k, r = self.weight.shape[0], self.weight.shape[2]
+        if not (USE_OWN_CONV and x.is_cuda and x.dtype == torch.float16 and self.stride == (1, 1)
+                and self.weight.shape[2] == self.weight.shape[3] and self.padding[0] == self.padding[1] and self.dilation[0] == self.dilation[1]
+                and 2 * self.padding[0] == self.dilation[0] * (r - 1) and _lib.load().pp_conv_own_supported(c, k, r)):
+            return None
+        L = _lib.load()
+
+        def run(bn):
+            if res is None and bn != PW_VARIANT:
+                return None                  # only the streaming 1x1 kernel has the two-output form without a residual (mode 5)
+            xx, rr, oo = _cl(x), (_cl(res) if res is not None else None), _cl(other)
+            dmode = 4 if res is not None else 5
+            wt, y = self._w(), self._out(x, h, w)
+            y2 = torch.empty_like(y, memory_format=torch.channels_last)
+            if bn == PW_VARIANT:   # the streaming 1x1 kernel, optionally with the SE gains of `x` folded into its input read
+                if not (USE_PW and r == 1 and self.padding[0] == 0 and L.pp_pw_supported(c, k)):
+                    return None
+                if pool_ok:   # ... and the 2x2 max-pool of y2 (the next stage's hourglass pools its input first)
+                    pooled = self._out(x, h // 2, w // 2)
+                    rc = L.pp_pw_pool_f16(_ptr(xx), _ptr(scale), _ptr(wt), _ptr(self.bias), _ptr(rr), _ptr(oo), _ptr(y), _ptr(y2),
+                                          _ptr(pooled), n * h * w, h * w, w, c, k, k, dmode, self._slope, _stream(x))
+                    return (y, y2, pooled) if rc == 0 else None
+                rc = L.pp_pw_f16(_ptr(xx), _ptr(scale), _ptr(wt), _ptr(self.bias), _ptr(rr), _ptr(oo), _ptr(y), _ptr(y2), n * h * w, h * w,
+                                 c, k, k, dmode, self._slope, _stream(x))
+            elif scale is not None:
+                return None
+            else:
+                rc = L.pp_conv_own_ex_f16(_ptr(xx), _ptr(wt), _ptr(self.bias), _ptr(rr), _ptr(oo), _ptr(y), _ptr(y2), n, h, w, c, k, r,
+                                          self.padding[0], self.dilation[0], 4, self._slope, bn, 0, _stream(x))
+            if rc != 0:
+                return None
+            return (y, y2, maxpool2(y2)) if want_pool else (y, y2)
+        return run
+
     def forward_dual(self, x, res, other, want_pool: bool = False):
         """-> (y, y + other) with y = act(conv(x) + bias + res).  One launch with two stores when that beats the fused
         convolution followed by a tensor add, timed once per shape.  x may be a Scaled pair (activation, SE gains)."""
-        from . import _lib
         scale = None
         if isinstance(x, Scaled):
             x, scale = x.y, x.s
@@ -552,82 +603,17 @@ class FConv(nn.Module):
         key = ("dual", n, c, h, w, k, r, self.padding[0], self.dilation[0], bool(self.act), scale is not None, pool_ok)
         if res is None:
             key = key + ("nores",)
-        ok = (USE_OWN_CONV and x.is_cuda and x.dtype == torch.float16 and self.stride == (1, 1)
-              and self.weight.shape[2] == self.weight.shape[3] and self.padding[0] == self.padding[1] and self.dilation[0] == self.dilation[1]
-              and 2 * self.padding[0] == self.dilation[0] * (r - 1) and _lib.load().pp_conv_own_supported(c, k, r))
 
         def separate():
             y = self(x if scale is None else channel_scale(x, scale), res)
             y2 = y + other
             return (y, y2, maxpool2(y2)) if want_pool else (y, y2)
 
-        def fused(bn):
-            if res is None and bn != PW_VARIANT:
-                return None                  # only the streaming 1x1 kernel has the two-output form without a residual (mode 5)
-            xx, rr, oo = _cl(x), (_cl(res) if res is not None else None), _cl(other)
-            dmode = 4 if res is not None else 5
-            if not self.weight.is_contiguous(memory_format=torch.channels_last):
-                self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
-            y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            y2 = torch.empty_like(y, memory_format=torch.channels_last)
-            if bn == PW_VARIANT:   # the streaming 1x1 kernel, optionally with the SE gains of `x` folded into its input read
-                if not (USE_PW and r == 1 and self.padding[0] == 0 and _lib.load().pp_pw_supported(c, k)):
-                    return None
-                if pool_ok:   # ... and the 2x2 max-pool of y2 (the next stage's hourglass pools its input first)
-                    pooled = torch.empty((n, k, h // 2, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-                    rc = _lib.load().pp_pw_pool_f16(_ptr(xx), _ptr(scale), _ptr(self.weight), _ptr(self.bias), _ptr(rr), _ptr(oo),
-                                                    _ptr(y), _ptr(y2), _ptr(pooled), n * h * w, h * w, w, c, k, k, dmode,
-                                                    LEAK if self.act else 1.0, _stream(x))
-                    return (y, y2, pooled) if rc == 0 else None
-                rc = _lib.load().pp_pw_f16(_ptr(xx), _ptr(scale), _ptr(self.weight), _ptr(self.bias), _ptr(rr), _ptr(oo), _ptr(y),
-                                           _ptr(y2), n * h * w, h * w, c, k, k, dmode, LEAK if self.act else 1.0, _stream(x))
-                if rc != 0:
-                    return None
-                return (y, y2, maxpool2(y2)) if want_pool else (y, y2)
-            if scale is not None:
-                return None
-            rc = _lib.load().pp_conv_own_ex_f16(_ptr(xx), _ptr(self.weight), _ptr(self.bias), _ptr(rr), _ptr(oo), _ptr(y), _ptr(y2), n, h, w,
-                                                c, k, r, self.padding[0], self.dilation[0], 4, LEAK if self.act else 1.0, bn, 0, _stream(x))
-            if rc != 0:
-                return None
-            return (y, y2, maxpool2(y2)) if want_pool else (y, y2)
-
-        choice = _conv_choice.get(key) if ok else 0
-        if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                return separate()
-            separate()                      # tunes the plain convolution's shape first
-
-            def timed(fn):
-                fn()
-                torch.cuda.synchronize()
-                ts = []
-                for _ in range(_TUNE_REPS):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    fn()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    ts.append(e0.elapsed_time(e1))
-                return sorted(ts)[len(ts) // 2]
-            times = {"separate": timed(separate)}
-            choice, best = 0, times["separate"]
-            for bn in (256, 128, 64, 512, PW_VARIANT):
-                if bn != PW_VARIANT and k % (bn if bn != 512 else 128):
-                    continue
-                if fused(bn) is None:
-                    continue
-                times[bn] = timed(lambda: fused(bn))
-                if times[bn] < best:
-                    choice, best = bn, times[bn]
-            _conv_timing[key] = times
-            _conv_choice[key] = choice
-            _note(key, choice)
-        if choice:
-            out = fused(choice)
-            if out is not None:
-                return out
-        return separate()
+        run = self._dual_fused(x, scale, res, other, want_pool, pool_ok)
+        choice = _choose(key, run is not None, [(0, "separate", separate)] + [
+            (bn, bn, lambda bn=bn: run(bn)) for bn in (256, 128, 64, 512, PW_VARIANT) if bn == PW_VARIANT or not k % (bn if bn != 512 else 128)])
+        out = run(choice) if choice else None
+        return separate() if out is None else out
 
     def forward_scaled(self, xs: "Scaled", res=None):
         """act(conv1x1(xs.y * xs.s) + bias (+ res)) with the gains folded into the kernel's input read; None when not taken"""
@@ -638,42 +624,31 @@ class FConv(nn.Module):
         if not (USE_PW and USE_OWN_CONV and x.is_cuda and x.dtype == torch.float16 and tuple(self.weight.shape[2:]) == (1, 1)
                 and self.stride == (1, 1) and self.padding == (0, 0) and (h * w) % 64 == 0 and _lib.load().pp_pw_supported(c, k)):
             return None
-        if not self.weight.is_contiguous(memory_format=torch.channels_last):
-            self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
-        y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        y = self._out(x, h, w)
         res = _cl(res) if res is not None else None
-        rc = _lib.load().pp_pw_f16(_ptr(x), _ptr(sc), _ptr(self.weight), _ptr(self.bias), _ptr(res), None, _ptr(y), None, n * h * w,
-                                   h * w, c, k, k, 1 if res is not None else 0, LEAK if self.act else 1.0, _stream(x))
+        rc = _lib.load().pp_pw_f16(_ptr(x), _ptr(sc), _ptr(self._w()), _ptr(self.bias), _ptr(res), None, _ptr(y), None, n * h * w,
+                                   h * w, c, k, k, 1 if res is not None else 0, self._slope, _stream(x))
         return y if rc == 0 else None
 
-    def forward_mean(self, x, partial: bool = False):
-        """-> (y, channel mean of y (n, c_out)) with y = act(conv(x) + bias): the SE squeeze of models/layers_transposed.py:298-303.
-        On the 3x3 halo-tile kernel the per-tile channel sums leave the convolution's epilogue (pp_conv_own_sums_f16) and only a
-        tiny reduction follows; timed once per shape against convolution + the two-pass channel mean.
-        partial=True: the fused form hands over the partial sums themselves, (ws (n, splits, c_out) fp32, splits, h * w), for a
-        consumer that finishes them on the way (FSE / pp_se_gains_f16)."""
-        from . import _lib
+    def _mean_fused(self, x):
+        """forward_mean's one-launch form, where it applies: run(hand_over) -> (y, mean) or (y, (partial sums, splits, h * w)),
+        or None when the kernel refuses the shape"""
         n, c, h, w = x.shape
         k = self.weight.shape[0]
-        key = ("mean", n, c, h, w, k, bool(self.act))
-        L = _lib.load() if x.is_cuda else None
-        splits = L.pp_conv_own_sums_splits(h, w) if L is not None else 0
-        ok = (USE_OWN_CONV and USE_SUM_FUSION and x.is_cuda and x.dtype == torch.float16 and self.stride == (1, 1) and splits > 0
-              and tuple(self.weight.shape[2:]) == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1)
-              and c % 32 == 0 and k % 64 == 0)
+        if not (USE_OWN_CONV and USE_SUM_FUSION and x.is_cuda and x.dtype == torch.float16 and self.stride == (1, 1)
+                and tuple(self.weight.shape[2:]) == (3, 3) and self.padding == (1, 1) and self.dilation == (1, 1)
+                and c % 32 == 0 and k % 64 == 0):
+            return None
+        from . import _lib
+        L = _lib.load()
+        splits = L.pp_conv_own_sums_splits(h, w)
+        if splits <= 0:
+            return None
 
-        def separate():
-            y = self(x)
-            return y, channel_mean(y)
-
-        def fused(hand_over=False):
-            xx = _cl(x)
-            if not self.weight.is_contiguous(memory_format=torch.channels_last):
-                self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
-            y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        def run(hand_over=False):
+            xx, y = _cl(x), self._out(x, h, w)
             ws = torch.empty((n, splits, k), dtype=torch.float32, device=x.device)
-            rc = L.pp_conv_own_sums_f16(_ptr(xx), _ptr(self.weight), _ptr(self.bias), _ptr(y), _ptr(ws), n, h, w, c, k,
-                                        LEAK if self.act else 1.0, _stream(x))
+            rc = L.pp_conv_own_sums_f16(_ptr(xx), _ptr(self._w()), _ptr(self.bias), _ptr(y), _ptr(ws), n, h, w, c, k, self._slope, _stream(x))
             if rc != 0:
                 return None
             if hand_over:
@@ -681,72 +656,59 @@ class FConv(nn.Module):
             mean = torch.empty((n, k), dtype=x.dtype, device=x.device)
             _lib.check(L.pp_channel_mean_finish_f16(_ptr(ws), _ptr(mean), n, h * w, k, splits, _stream(x)))
             return y, mean
+        return run
 
-        choice = _conv_choice.get(key) if ok else 0
-        if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                return separate()
-            separate()
-            if fused() is None:
-                choice = 0
-            else:
-                t_sep, t_fused = _timed(separate), _timed(fused)
-                _conv_timing[key] = {"separate": t_sep, "fused": t_fused}
-                choice = 1 if t_fused < t_sep else 0
-            _conv_choice[key] = choice
-            _note(key, choice)
-        if choice:
-            out = fused(partial)
-            if out is not None:
-                return out
-        return separate()
+    def forward_mean(self, x, partial: bool = False):
+        """-> (y, channel mean of y (n, c_out)) with y = act(conv(x) + bias): the SE squeeze of models/layers_transposed.py:298-303.
+        On the 3x3 halo-tile kernel the per-tile channel sums leave the convolution's epilogue (pp_conv_own_sums_f16) and only a
+        tiny reduction follows; timed once per shape (with that reduction) against convolution + the two-pass channel mean.
+        partial=True: the fused form hands over the partial sums themselves, (ws (n, splits, c_out) fp32, splits, h * w), for a
+        consumer that finishes them on the way (FSE / pp_se_gains_f16)."""
+        n, c, h, w = x.shape
+        key = ("mean", n, c, h, w, self.weight.shape[0], bool(self.act))
+
+        def separate():
+            y = self(x)
+            return y, channel_mean(y)
+
+        run = self._mean_fused(x)
+        out = run(partial) if _choose(key, run is not None, [(0, "separate", separate), (1, "fused", run)]) else None
+        return separate() if out is None else out
+
+    def _pool_fused(self, x, res):
+        """forward_pool's one-launch form, where it applies: run() -> (y, pooled), or None when the kernel refuses the shape"""
+        from . import _lib
+        n, c, h, w = x.shape
+        k = self.weight.shape[0]
+        if not (USE_PW and USE_POOL_FUSION and USE_OWN_CONV and x.is_cuda and x.dtype == torch.float16 and self.stride == (1, 1)
+                and tuple(self.weight.shape[2:]) == (1, 1) and self.padding == (0, 0) and h % 2 == 0
+                and w % (64 if c == 64 else 32) == 0 and _lib.load().pp_pw_supported(c, k)):
+            return None
+
+        def run():
+            xx = _cl(x)
+            rr = _cl(res) if res is not None else None
+            y, pooled = self._out(x, h, w), self._out(x, h // 2, w // 2)
+            rc = _lib.load().pp_pw_pool_f16(_ptr(xx), None, _ptr(self._w()), _ptr(self.bias), _ptr(rr), None, _ptr(y), None,
+                                            _ptr(pooled), n * h * w, h * w, w, c, k, k, 1 if res is not None else 0,
+                                            self._slope, _stream(x))
+            return (y, pooled) if rc == 0 else None
+        return run
 
     def forward_pool(self, x, res=None):
         """-> (y, maxpool2(y)) with y = act(conv(x) + bias (+ res)).  For a 1x1 convolution the pooled tensor can leave the
         streaming kernel as one more output (pp_pw_pool_f16) instead of a pass of its own; timed once per shape against
         convolution + k_maxpool2."""
-        from . import _lib
         n, c, h, w = x.shape
-        k = self.weight.shape[0]
-        key = ("pool", n, c, h, w, k, res is not None, bool(self.act))
-        ok = (USE_PW and USE_POOL_FUSION and USE_OWN_CONV and x.is_cuda and x.dtype == torch.float16 and self.stride == (1, 1)
-              and tuple(self.weight.shape[2:]) == (1, 1) and self.padding == (0, 0) and h % 2 == 0
-              and w % (64 if c == 64 else 32) == 0 and _lib.load().pp_pw_supported(c, k))
+        key = ("pool", n, c, h, w, self.weight.shape[0], res is not None, bool(self.act))
 
         def separate():
             y = self(x, res)
             return y, maxpool2(y)
 
-        def fused():
-            xx = _cl(x)
-            rr = _cl(res) if res is not None else None
-            if not self.weight.is_contiguous(memory_format=torch.channels_last):
-                self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
-            y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            pooled = torch.empty((n, k, h // 2, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            rc = _lib.load().pp_pw_pool_f16(_ptr(xx), None, _ptr(self.weight), _ptr(self.bias), _ptr(rr), None, _ptr(y), None,
-                                            _ptr(pooled), n * h * w, h * w, w, c, k, k, 1 if res is not None else 0,
-                                            LEAK if self.act else 1.0, _stream(x))
-            return (y, pooled) if rc == 0 else None
-
-        choice = _conv_choice.get(key) if ok else 0
-        if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                return separate()
-            separate()                      # tunes the plain convolution's shape first
-            if fused() is None:
-                choice = 0
-            else:
-                t_sep, t_fused = _timed(separate), _timed(fused)
-                _conv_timing[key] = {"separate": t_sep, "fused": t_fused}
-                choice = 1 if t_fused < t_sep else 0
-            _conv_choice[key] = choice
-            _note(key, choice)
-        if choice:
-            out = fused()
-            if out is not None:
-                return out
-        return separate()
+        run = self._pool_fused(x, res)
+        out = run() if _choose(key, run is not None, [(0, "separate", separate), (1, "fused", run)]) else None
+        return separate() if out is None else out
 
     def forward(self, x, res=None, post=None, out=None):
         """act(conv(x) + bias (+ res)) (+ post); out: optional destination, e.g. a channel slice of a wider channels-last tensor"""
@@ -771,7 +733,7 @@ class FConv(nn.Module):
             x = _cl(x)
             n, k, h, w = x.shape
             cout = self.weight.shape[0]
-            y = torch.empty((n, cout, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+            y = self._out(x, h, w)
             res = _cl(res) if res is not None else None
             post = _cl(post) if post is not None else None
             _lib.check(_lib.load().pp_pwconv_f16(_ptr(x), _ptr(self.weight), _ptr(self.bias), _ptr(res), _ptr(post), _ptr(y),
@@ -809,9 +771,9 @@ class FStem(FConv):
             _fallback("stem", x, "needs an fp16 NHWC image with even height and width % 4 == 0")
             return super().forward(x, res, post)
         from . import _lib
-        y = torch.empty((n, 64, h // 2, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        y = self._out(x, h // 2, w // 2)
         _lib.check(_lib.load().pp_stem7x7_f16(_ptr(x), _ptr(self.prepared), _ptr(self.bias), _ptr(y), n, h, w,
-                                              LEAK if self.act else 1.0, _stream(x)))
+                                              self._slope, _stream(x)))
         return y
 
 
@@ -842,11 +804,9 @@ class FHead(FConv):
         ok = (USE_PW and USE_OWN_CONV and res is None and post is None and xx.is_cuda and xx.dtype == torch.float16
               and tuple(self.weight.shape[2:]) == (1, 1) and (xs is None or (h * w) % 64 == 0) and _lib.load().pp_pw_supported(c, kp))
         if ok:
-            if not self.wpad.is_contiguous(memory_format=torch.channels_last):
-                self.wpad.data = self.wpad.data.contiguous(memory_format=torch.channels_last)
-            y = torch.empty((n, kp, h, w), dtype=xx.dtype, device=xx.device, memory_format=torch.channels_last)
-            rc = _lib.load().pp_pw_f16(_ptr(xx), _ptr(xs.s.contiguous()) if xs is not None else None, _ptr(self.wpad), _ptr(self.bpad),
-                                       None, None, _ptr(y), None, n * h * w, h * w, c, kp, kp, 0, LEAK if self.act else 1.0,
+            y = self._out(xx, h, w, kp)
+            rc = _lib.load().pp_pw_f16(_ptr(xx), _ptr(xs.s.contiguous()) if xs is not None else None, _ptr(self._w("wpad")), _ptr(self.bpad),
+                                       None, None, _ptr(y), None, n * h * w, h * w, c, kp, kp, 0, self._slope,
                                        _stream(xx))
             if rc == 0:
                 self.last_padded = y           # the 64-channel tensor behind the view (channels 50..63 are exact zeros)
@@ -888,10 +848,8 @@ class FResidual(nn.Module):
         res = self.skip.conv_only(x) if self.skip is not None else x
         return self.c3.forward_pool(self.c2(self.c1(x)), res)
 
-    def _cat(self, x, want_pool):
-        """conv3(t) + skip(x) as ONE product over the concatenated channels [t ; x] (pp_pw_cat_f16) when both weight matrices fit
-        the streaming kernel's LDS in one piece (otherwise the input would be read once per output-channel split and nothing is
-        gained); timed once per shape against the unfused form.  -> (y, pooled or None), or None."""
+    def _cat_fused(self, x, want_pool, pool_ok):
+        """_cat's one-launch form, where it applies: run() -> (y, pooled or None), or None when the kernel refuses the shape"""
         from . import _lib
         if not (USE_PW and USE_CAT_SKIP and USE_OWN_CONV and x.is_cuda and x.dtype == torch.float16):
             return None
@@ -899,46 +857,44 @@ class FResidual(nn.Module):
         c2 = self.skip.weight.shape[1]
         n, _, h, w = x.shape
         # (weights beyond 144 KB split the output channels over workgroup columns that read the same pixels at about the same
-        # time -- the re-reads are served by the cache hierarchy; the timing below decides)
+        # time -- the re-reads are served by the cache hierarchy; the timing decides)
         if (tuple(self.skip.weight.shape[2:]) != (1, 1) or self.skip.stride != (1, 1)
                 or not _lib.load().pp_pw_supported(c1 + c2, k) or c1 % 32 or c2 % 32):
             return None
-        # (beyond 512 input channels the kernel works on 16-pixel groups, which have no 2-row form to pool)
-        pool_ok = want_pool and USE_POOL_FUSION and h % 2 == 0 and w % (64 if c1 + c2 == 64 else 32) == 0 and c1 + c2 <= 512
-        key = ("cat", n, c1, c2, h, w, k, bool(self.c3.act), pool_ok)
         if getattr(self, "_wcat", None) is None or self._wcat.device != x.device:
             self._wcat = torch.cat([self.c3.weight.detach().flatten(1), self.skip.weight.detach().flatten(1)], dim=1).contiguous()
+
+        def run():
+            t = _cl(self.c2(self.c1(x)))
+            xx, y = _cl(x), self.c3._out(x, h, w)
+            pooled = self.c3._out(x, h // 2, w // 2) if pool_ok else None
+            rc = _lib.load().pp_pw_cat_f16(_ptr(t), _ptr(xx), _ptr(self._wcat), _ptr(self.c3.bias), None, _ptr(y), _ptr(pooled), n * h * w,
+                                           h * w, w if pool_ok else 0, c1, c2, k, k, 0, self.c3._slope, _stream(x))
+            if rc != 0:
+                return None
+            return y, (pooled if pool_ok else (maxpool2(y) if want_pool else None))
+        return run
+
+    def _cat(self, x, want_pool):
+        """conv3(t) + skip(x) as ONE product over the concatenated channels [t ; x] (pp_pw_cat_f16) when both weight matrices fit
+        the streaming kernel's LDS in one piece (otherwise the input would be read once per output-channel split and nothing is
+        gained); timed once per shape against the unfused form.  -> (y, pooled or None), or None."""
+        k, c1 = self.c3.weight.shape[:2]
+        c2 = self.skip.weight.shape[1]
+        n, _, h, w = x.shape
+        # (beyond 512 input channels the kernel works on 16-pixel groups, which have no 2-row form to pool)
+        pool_ok = want_pool and USE_POOL_FUSION and h % 2 == 0 and w % (64 if c1 + c2 == 64 else 32) == 0 and c1 + c2 <= 512
+        run = self._cat_fused(x, want_pool, pool_ok)
+        if run is None:
+            return None
+        key = ("cat", n, c1, c2, h, w, k, bool(self.c3.act), pool_ok)
 
         def separate():
             res = self.skip.conv_only(x)
             t = self.c2(self.c1(x))
             return self.c3.forward_pool(t, res) if want_pool else (self.c3(t, res), None)
 
-        def fused():
-            t = _cl(self.c2(self.c1(x)))
-            xx = _cl(x)
-            y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            pooled = torch.empty((n, k, h // 2, w // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if pool_ok else None
-            rc = _lib.load().pp_pw_cat_f16(_ptr(t), _ptr(xx), _ptr(self._wcat), _ptr(self.c3.bias), None, _ptr(y), _ptr(pooled), n * h * w,
-                                           h * w, w if pool_ok else 0, c1, c2, k, k, 0, LEAK if self.c3.act else 1.0, _stream(x))
-            if rc != 0:
-                return None
-            return y, (pooled if pool_ok else (maxpool2(y) if want_pool else None))
-
-        choice = _conv_choice.get(key)
-        if choice is None:
-            if torch.cuda.is_current_stream_capturing():
-                return None
-            separate()
-            if fused() is None:
-                choice = 0
-            else:
-                t_sep, t_fused = _timed(separate), _timed(fused)
-                _conv_timing[key] = {"separate": t_sep, "fused": t_fused}
-                choice = 1 if t_fused < t_sep else 0
-            _conv_choice[key] = choice
-            _note(key, choice)
-        return fused() if choice else None
+        return run() if _choose(key, True, [(0, "separate", separate), (1, "fused", run)]) else None
 
 
 class FHourglass(nn.Module):

@@ -1154,3 +1154,55 @@ def test_se_excitation_kernel_matches_the_torch_modules(shape):
     torch.cuda.synchronize()
     assert (a.float() - want).abs().max().item() <= 1.5e-3 and (b.float() - want).abs().max().item() <= 1.5e-3
     assert L.pp_se_gains_f16(vp(ws.data_ptr()), vp(mean.data_ptr()), *args, vp(a.data_ptr()), n, hw, c, hid, splits, 0.01, st) == -2
+
+
+def _choice_in_domain(key, v, n_templates):
+    from posepaf import fused_model as fm
+    form = key[0] if isinstance(key[0], str) else "plain"
+    if form == "plain":
+        return v == -1 or 0 <= v < n_templates or v in fm.OWN_VARIANTS or v == fm.PW_VARIANT
+    return v in {"up2": range(2 + len(fm.UP2_COLLAPSED_BN)), "dual": (0, 256, 128, 64, 512, fm.PW_VARIANT)}.get(form, (0, 1))
+
+
+def test_tuning_pass_table_hits_and_graph_capture_run_the_same_kernels():
+    """One forward from empty tables (tunes every shape), one more (table hits only) and one through GraphedForward give the
+    same bits; the second pass adds no key; the table survives table_entries -> install_entries, directly and through JSON,
+    every stored value lies in its form's encoding; and the key set is the one the tuner produced before the six tuning sites
+    became one protocol (profiles/r07_tuner_keys_2x128x128.json: the sorted table_entries() keys of that commit for this input).
+    Four skip convolutions of the deepest hourglass levels (512 / 640 / 768 channels: more than the two-input 1x1 kernel takes)
+    stay on MIOpen, whose default fp16 kernel for them is not repeatable from call to call (measured alone, outside the model:
+    three calls on one input, three results) -- torch.backends.cudnn.deterministic asks MIOpen for a repeatable one, so that
+    the comparison sees the kernels this project chooses."""
+    import json
+    import os
+    from conftest import ROOT
+    from posepaf import _lib, fused_model as fm
+    saved = (fm._conv_choice, fm._conv_timing, fm._conv_calls, torch.backends.cudnn.deterministic)
+    x = torch.from_numpy(np.random.default_rng(4).random((2, 128, 128, 3), dtype=np.float32)).cuda().half()
+    try:
+        torch.backends.cudnn.deterministic = True
+        fm._conv_choice, fm._conv_timing, fm._conv_calls = {}, {}, {}
+        model = fm.build_inference_model(torch.device("cuda", 0))
+        with torch.no_grad():
+            first = model(x).clone()
+            table = dict(fm._conv_choice)
+            second = model(x).clone()
+            assert fm._conv_choice == table, sorted(map(str, set(fm._conv_choice) - set(table)))
+            graphed = fm.GraphedForward(model, x)(x).clone()
+        torch.cuda.synchronize()
+        assert fm._conv_choice == table and set(fm._conv_timing) <= set(table)
+        assert first.shape == (2, 50, 32, 32) and torch.isfinite(first).all()
+        assert torch.equal(first, second), (first.float() - second.float()).abs().max().item()
+        assert torch.equal(second, graphed), (second.float() - graphed.float()).abs().max().item()
+        entries = fm.table_entries()
+        for form in (entries, json.loads(json.dumps(entries))):
+            fm._conv_choice = {}
+            assert fm.install_entries(form) == len(table) and fm._conv_choice == table
+        n_templates = _lib.load().pp_conv_num_configs()
+        bad = {k: v for k, v in table.items() if not _choice_in_domain(k, v, n_templates)}
+        assert not bad, bad
+        want = json.load(open(os.path.join(ROOT, "profiles", "r07_tuner_keys_2x128x128.json")))
+        assert json.loads(json.dumps([e[0] for e in entries])) == want
+    finally:
+        fm._conv_choice, fm._conv_timing, fm._conv_calls = saved[:3]
+        torch.backends.cudnn.deterministic = saved[3]
