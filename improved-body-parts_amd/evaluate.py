@@ -6,6 +6,7 @@
     python evaluate.py --gpus 8 --run_refactor --run_cpp --synthetic 5000          # launches its own 8 ranks
     python evaluate.py --synthetic 512 --batch 32 --scales 1.0 --test_cfg thre2=0.05 mid_num=40 remove_recon=1   # original
         path with the reference's test_cfg keys as run-time values (or --config_file PATH: the [param] section of an INI file)
+    python evaluate.py --run_refactor --run_cpp --synthetic 256 --render_dir out/    # + every image with its skeletons drawn
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --synthetic 5000 ...
 
 What is kept from the reference: the flags --run_refactor / --run_cpp (:53-54; --run_cpp selects the C++ pafprocess rules --
@@ -89,6 +90,13 @@ def parse(argv=None):
     ap.add_argument("--config_file", default=None, metavar="PATH",
                     help="without --run_refactor: take those values from the [param] section of a file in the reference's INI "
                          "layout (utils/config); --test_cfg entries override it")
+    ap.add_argument("--render_dir", default=None, metavar="DIR",
+                    help="with --run_refactor: draw every image's skeletons on the GPU (pp_draw_humans_u8, the refactored branch "
+                         "of demo_image.py:174-192, inside the batch's graph) and write each image's own (h, w) canvas to "
+                         "DIR/<index in the set>.npy (BGR uint8).  The original path's ellipse drawing stays in demo_image.py and "
+                         "refuses the option")
+    ap.add_argument("--render_format", choices=("npy", "png"), default="npy",
+                    help="file format of --render_dir: .npy always works, .png goes through PIL (as demo_image.save_image)")
     a = ap.parse_args(argv)
     a.test_cfg_dict = None
     if a.test_cfg is not None or a.config_file is not None:
@@ -262,7 +270,7 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
     groups = buckets_by_padded_shape(shapes)
     max_hw = (max([padded_shape(*s)[0] for s in shapes] + [64]), max([padded_shape(*s)[1] for s in shapes] + [64]))
     eng = InferenceEngine(model, post, B, dev.index, rules="cpp" if a.run_cpp else "py", use_graph=not a.no_graph,
-                          inject_scale=1e-3 if src.has_scenes else None, max_image_hw=max_hw,
+                          inject_scale=1e-3 if src.has_scenes else None, max_image_hw=max_hw, render=bool(a.render_dir),
                           progress=(lambda m: print(f"[evaluate] {m}", file=sys.stderr, flush=True)) if rank == 0 else None)
     jobs = []
     for (hp, wp), members in groups.items():
@@ -304,6 +312,10 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
             idx[j] = bank_slot[i]
 
     workers = a.workers or max(1, min(16, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 8) // max(1, min(world, 8))))
+    n_rendered = 0
+    if a.render_dir:
+        from demo_image import save_image
+        os.makedirs(a.render_dir, exist_ok=True)
     eng.sync()
     if world > 1:
         import torch.distributed as dist
@@ -314,11 +326,19 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
         rec = eng.submit(slot, plan)
         local.index_copy_(0, torch.as_tensor(loc, dtype=torch.int64).to(dev, non_blocking=True),
                           rec.view(plan.b, RECORD_BYTES)[: len(loc)])
+        if a.render_dir:   # the canvas is the plan's until its next submit: bring it to the host now (waits for this batch)
+            canvases = plan.canvas[: len(loc)].cpu().numpy()
+            for j, k_local in enumerate(loc):
+                h, w = shapes[k_local]
+                save_image(os.path.join(a.render_dir, "%06d.%s" % (int(mine[k_local]), a.render_format)), canvases[j, :h, :w])
+                n_rendered += 1
     eng.sync()
     dt = time.perf_counter() - t0
     feeder.close()
     info = {"plans": sorted(eng.plans), "decode_threads": workers,
             "conv_table": fused_model.table_hash(), "launch": "eager" if a.no_graph else "hipGraph replay"}
+    if a.render_dir:
+        info["rendered_files"] = n_rendered
     if a.run_cpp:   # where pp_process_batch kept the maps it was handed (dtype and shape of each bucket's network output)
         kinds = {post.map_residency(p.maps.dtype, p.maps.shape[3], p.maps.shape[4]) for p in eng.plans.values() if p.maps is not None}
         if kinds:
@@ -458,6 +478,9 @@ def main(argv=None):
     if a.test_cfg_dict is not None and not original:
         raise SystemExit("--test_cfg / --config_file run on the original path only (drop --run_refactor): the refactored path's "
                          "captured graphs are built for the INI defaults")
+    if a.render_dir is not None and original:
+        raise SystemExit("--render_dir draws from the records of the refactored path only (add --run_refactor): the original "
+                         "path's ellipse / alpha-blend drawing (demo_image.py:218-240) stays on NumPy in demo_image.py")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -526,6 +549,10 @@ def main(argv=None):
         t = torch.tensor([dt_local], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+        if "rendered_files" in info:    # every rank wrote its own images
+            n = torch.tensor([info["rendered_files"]], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(n, op=dist.ReduceOp.SUM)
+            info["rendered_files"] = int(n.item())
     else:
         merged = records_to_numpy(local_recs[:len(mine) * RECORD_BYTES])
         dt = dt_local

@@ -35,7 +35,7 @@ EXPORTS = [
     "pp_get_part_score", "pp_get_status", "pp_py_find_connections_host", "pp_py_find_humans_host", "pp_original_accumulate", "pp_original_accumulate_all", "pp_original_finish",
     "pp_preprocess_u8_affine", "pp_original_accumulate_affine", "pp_original_accumulate_all_affine", "pp_warp_affine_f32",
     "pp_resize_u8_cubic", "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
-    "pp_set_map_residency", "pp_map_residency", "pp_map_workspace_bytes", "pp_time_map_prepass",
+    "pp_set_map_residency", "pp_map_residency", "pp_map_workspace_bytes", "pp_time_map_prepass", "pp_draw_humans_u8",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -105,6 +105,7 @@ def load():
     L.pp_channel_scale_f16.argtypes = [vp, vp, vp, C.c_int, C.c_long, C.c_int, vp]
     L.pp_preprocess_u8.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pp_preprocess_u8_ragged.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.pp_draw_humans_u8.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pp_flip_average.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_pwconv_supported.argtypes = [C.c_int, C.c_int]
     L.pp_pwconv_f16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int, vp]

@@ -5,7 +5,8 @@ evaluate.py:235-280), so the number the benchmark reports is the speed of the lo
 
     pinned host slot --(copy stream, H2D)--> staging ring --(HBM -> HBM)--> the plan's input buffer
         --> [HIP graph of the plan: pad / 255 / mirror (pp_preprocess_u8_ragged) -> IMHN forward (fp16) ->
-             (synthetic runs only: + scene bank[idx]) -> K_A -> K_B (+ assembly)] --> pp_record[b] of the plan
+             (synthetic runs only: + scene bank[idx]) -> K_A -> K_B (+ assembly)
+             (render=True only: -> pp_draw_humans_u8, the skeletons on the plan's canvas)] --> pp_record[b] of the plan
 
 A *plan* belongs to one bucket `(Hp, Wp, b)`: `b` images whose sizes pad to the same multiple-of-64 shape
 (utils/parse_skeletons.py:54, utils/util.py:44-65).  The reference runs every image alone at its own size; bucketing by
@@ -79,17 +80,21 @@ class _Plan:
         self.bank = None              # (K, 2, 50, hp/4, wp/4) fp16 synthetic scenes, or None
         self.graph = None
         self.maps = None              # the plan's last network output (kept for checks)
+        # render=True: the images of the batch with their skeletons drawn (each image's own corner; valid until the next submit)
+        self.canvas = torch.zeros((b, hp, wp, 3), dtype=torch.uint8, device=dev) if eng.render else None
 
 
 class InferenceEngine:
     """model: FusedIMHN-like module (NHWC fp16 in [0,1] -> (N, 50, h/4, w/4)); post: PosePostProcessor.
     rules: "cpp" = pafprocess rules (evaluate.py --run_cpp), "py" = find_connections + find_humans rules.
     inject_scale: synthetic runs add scene_bank[idx] to `inject_scale * network output` (a randomly initialised network emits
-    no peaks); None = the network output alone (real weights)."""
+    no peaks); None = the network output alone (real weights).
+    render: every plan also owns `canvas`, a (b, hp, wp, 3) uint8 device buffer, and the per-batch path ends with the skeletons
+    of the plan's records drawn from its images into that canvas (posepaf.render.draw_records, inside the captured graph)."""
 
     def __init__(self, model, post, batch: int, device: int, rules: str = "cpp", use_graph: bool = True,
                  inject_scale: float | None = None, max_image_hw=(512, 512), n_slots: int = 3, n_staging: int = 2,
-                 postproc_only: bool = False, progress=None):
+                 postproc_only: bool = False, progress=None, render: bool = False):
         if not torch.cuda.is_available():
             raise PosePafError("no HIP device: the engine has no CPU path")
         if rules not in ("cpp", "py"):
@@ -97,6 +102,7 @@ class InferenceEngine:
         self.model, self.post, self.B, self.rules = model, post, int(batch), rules
         self.dev = torch.device("cuda", device)
         self.use_graph, self.postproc_only, self.progress = use_graph, postproc_only, progress
+        self.render = bool(render)
         self.inject_scale = None if inject_scale is None else torch.tensor(inject_scale, dtype=torch.float16, device=self.dev)
         hp, wp = padded_shape(*max_image_hw)
         self.max_bytes = header_bytes(self.B) + self.B * hp * wp * 3
@@ -157,6 +163,9 @@ class InferenceEngine:
             self.post.process_async(maps, hp, True, min_img_size_dev=heights, records=p.records)
         else:
             self.post.process_py_async(maps, hp, True, img_height_dev=heights, records=p.records)
+        if self.render:
+            from .render import draw_records
+            draw_records(p.images, p.records, p.sizes, out=p.canvas)
         return p.records
 
     def prepare(self, plan: _Plan, warmup: int = 2):

@@ -328,6 +328,21 @@ PP_API int pp_preprocess_u8_affine(const void *images_u8, void *out, int dtype, 
 PP_API int pp_preprocess_u8_ragged(const void *images_u8, const int *sizes_dev, void *out, int dtype, int batch, int hp,
                                    int wp, int pad_value, int flip, void *stream);
 
+/* Demo rendering (reference demo_image.py:174-192, the refactored branch; utils/common.py:240-264 draw_humans with pixel
+ * coordinates): every human of every record drawn on its image in ONE launch -- per human the present joints 0..17 as discs of
+ * radius 4.5 in CocoColors[part] (utils/common.py:281-283), then CocoPairsRender (:285-289) as lines of thickness 3 in
+ * CocoColors[pair], later over earlier -- bit-equal to the NumPy renderer utils/draw.py:draw_humans(canvas, humans) (parity with
+ * cv2's own rasteriser stays unpinned, as for draw.py).  The ellipse / alpha-blend style of the original branch
+ * (demo_image.py:218-240) is not offered: its angle goes through atan2 / cos / sin.
+ * records_dev: DEVICE pp_record[batch]; n_humans is clamped to [0, PP_MAX_HUMANS], peak_id[p] < 0 = part absent, and with
+ * PP_ST_FLOAT_COORDS the joint is drawn at the truncated coordinate, as int(bp.x) does.  src_u8 / dst_u8: DEVICE (batch, hp, wp, 3)
+ * BGR; dst_u8 == src_u8 draws in place, any other overlap is the caller's error.  sizes_dev: DEVICE int[2][batch] = heights, then
+ * widths (the layout of pp_preprocess_u8_ragged), NULL = every image is hp x wp.  Only the top-left (h, w) corner of a slot is
+ * read or written: the rest of dst is left as it was, the rest of src is never read.  Bit-equality holds for coordinates within
+ * +-32767; beyond that nothing outside the image's pixels is written.  Asynchronous, nothing allocated: capturable. */
+PP_API int pp_draw_humans_u8(const pp_record *records_dev, const void *src_u8, void *dst_u8, const int *sizes_dev, int batch, int hp,
+                             int wp, void *stream);
+
 /* A2 standalone: the arrays predict_refactor returns (utils/parse_skeletons.py:82-103).  net_out_dev as for
  * pp_process_batch; heat_hwc_dev: DEVICE float[batch][h][w][20], paf_hwc_dev: DEVICE float[batch][h][w][30]. */
 PP_API int pp_flip_average(const void *net_out_dev, int dtype, int batch, int h, int w, int flip, float *heat_hwc_dev,
