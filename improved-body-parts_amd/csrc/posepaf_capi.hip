@@ -717,6 +717,55 @@ int pp_original_finish(pp_ctx *ctx, int batch, int img_h, int img_w, float thre1
     return PP_OK;
 }
 
+// ---- ragged buckets: images of different sizes that share the padded shape of every scale
+namespace {
+// sizes: HOST int[2][batch]; every image positive and within its slot
+bool ragged_sizes_ok(const int *sizes, int batch, long slot_area) {
+    for (int b = 0; b < batch; b++)
+        if (sizes[b] <= 0 || sizes[batch + b] <= 0 || (long)sizes[b] * sizes[batch + b] > slot_area) return false;
+    return true;
+}
+}  // namespace
+
+int pp_original_accumulate_all_ragged(pp_ctx *ctx, int batch, int n_scales, const void *const *net_out_dev, int dtype, const int *h,
+                                      const int *w, int flip, const int *sizes, const int *sizes_dev, const int *pads,
+                                      const int *pads_dev, long slot_area, double *heat_acc, double *paf_acc, void *stream) {
+    if (!ctx || !net_out_dev || !h || !w || !sizes || !sizes_dev || !pads || !pads_dev || !heat_acc || !paf_acc || batch <= 0 ||
+        slot_area <= 0 || n_scales <= 0 || (dtype != PP_F16 && dtype != PP_F32) || !ragged_sizes_ok(sizes, batch, slot_area))
+        return PP_ERR_BAD_ARG;
+    if (n_scales > 6) return PP_ERR_UNSUPPORTED;
+    for (int i = 0; i < n_scales; i++) {
+        if (!net_out_dev[i] || h[i] <= 0 || w[i] <= 0) return PP_ERR_BAD_ARG;
+        for (int b = 0; b < batch; b++) {
+            const int pd = pads[(i * 2) * batch + b], pr = pads[(i * 2 + 1) * batch + b];
+            if (pd < 0 || pr < 0 || pd >= 4 * h[i] || pr >= 4 * w[i]) return PP_ERR_BAD_ARG;
+        }
+    }
+    const hipError_t e = pp::launch_accumulate_scales_ragged(n_scales, net_out_dev, dtype, batch, h, w, flip, sizes, sizes_dev, pads,
+                                                             pads_dev, slot_area, heat_acc, paf_acc,
+                                                             static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return PP_ERR_UNSUPPORTED;   // an image whose tiles do not fit LDS: run exact-size groups
+    PP_HIP(ctx, e);
+    return PP_OK;
+}
+
+int pp_original_finish_ragged(pp_ctx *ctx, int batch, const int *sizes, const int *sizes_dev, long slot_area, float thre1,
+                              const double *heat_acc, const double *paf_acc, unsigned char *mask_scratch, void *peaks64_scratch,
+                              pp_record *records_dev, void *stream) {
+    if (!ctx || !sizes || !sizes_dev || !heat_acc || !paf_acc || !mask_scratch || !peaks64_scratch || batch <= 0 ||
+        batch > ctx->max_batch || slot_area <= 0 || !ragged_sizes_ok(sizes, batch, slot_area))
+        return PP_ERR_BAD_ARG;
+    if (pp::lds_bytes_assemble_py(ctx->maxp) > pp::kMaxDynLds) return PP_ERR_TOO_LARGE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    pp_record *rec = records_dev ? records_dev : ctx->d_records;
+    PP_HIP(ctx, pp::launch_fullres(batch, 0, 0, thre1, ctx->maxp, ctx->cap, 0, heat_acc, paf_acc, mask_scratch, peaks64_scratch,
+                                   ctx->d_counts, ctx->d_conns_py, ctx->d_conn_counts, ctx->d_status, rec, ctx->py_cfg(), st,
+                                   sizes_dev, slot_area));
+    ctx->last_stream = st;
+    ctx->last_batch = batch;
+    return PP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ run-time test configuration
 int pp_default_test_cfg(pp_test_cfg *cfg) {
     if (!cfg) return PP_ERR_BAD_ARG;

@@ -716,6 +716,41 @@ __device__ __forceinline__ void cubic_coeffs_i(float x, int c[4]) {
 }
 __device__ __forceinline__ int clampi_e(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// one output pixel (dy, dx) of an image whose source is sh x sw with rows of src_ld pixels; o: its 3 bytes
+__device__ __forceinline__ void resize_u8_pixel(const unsigned char *__restrict__ src, int sh, int sw, long src_ld, int dy, int dx,
+                                                double scale_x, double scale_y, unsigned char *__restrict__ o) {
+    float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
+    const int sx = (int)floorf(fx);
+    fx = __fadd_rn(fx, -(float)sx);
+    float fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    fy = __fadd_rn(fy, -(float)sy);
+    int ia[4], ib[4];
+    cubic_coeffs_i(fx, ia);
+    cubic_coeffs_i(fy, ib);
+    int acc[3] = {0, 0, 0};
+#pragma unroll
+    for (int ky = 0; ky < 4; ky++) {
+        const unsigned char *row = src + ((long)clampi_e(sy - 1 + ky, 0, sh - 1) * src_ld) * 3;
+        int hs[3] = {0, 0, 0};
+#pragma unroll
+        for (int kx = 0; kx < 4; kx++) {
+            const unsigned char *p = row + (long)clampi_e(sx - 1 + kx, 0, sw - 1) * 3;
+            hs[0] += (int)p[0] * ia[kx];
+            hs[1] += (int)p[1] * ia[kx];
+            hs[2] += (int)p[2] * ia[kx];
+        }
+        acc[0] += hs[0] * ib[ky];
+        acc[1] += hs[1] * ib[ky];
+        acc[2] += hs[2] * ib[ky];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int v = (acc[c] + (1 << 21)) >> 22;
+        o[c] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    }
+}
+
 __global__ __launch_bounds__(256) void k_resize_u8(const unsigned char *__restrict__ src, unsigned char *__restrict__ dst, int B,
                                                    int sh, int sw, int dh, int dw, double scale_x, double scale_y) {
     const long total = (long)B * dh * dw;
@@ -725,37 +760,27 @@ __global__ __launch_bounds__(256) void k_resize_u8(const unsigned char *__restri
         long t = i / dw;
         const int dy = (int)(t % dh);
         const long b = t / dh;
-        float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
-        const int sx = (int)floorf(fx);
-        fx = __fadd_rn(fx, -(float)sx);
-        float fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
-        const int sy = (int)floorf(fy);
-        fy = __fadd_rn(fy, -(float)sy);
-        int ia[4], ib[4];
-        cubic_coeffs_i(fx, ia);
-        cubic_coeffs_i(fy, ib);
-        int acc[3] = {0, 0, 0};
-#pragma unroll
-        for (int ky = 0; ky < 4; ky++) {
-            const unsigned char *row = src + ((b * sh + clampi_e(sy - 1 + ky, 0, sh - 1)) * (long)sw) * 3;
-            int hs[3] = {0, 0, 0};
-#pragma unroll
-            for (int kx = 0; kx < 4; kx++) {
-                const unsigned char *p = row + (long)clampi_e(sx - 1 + kx, 0, sw - 1) * 3;
-                hs[0] += (int)p[0] * ia[kx];
-                hs[1] += (int)p[1] * ia[kx];
-                hs[2] += (int)p[2] * ia[kx];
-            }
-            acc[0] += hs[0] * ib[ky];
-            acc[1] += hs[1] * ib[ky];
-            acc[2] += hs[2] * ib[ky];
-        }
-        unsigned char *o = dst + i * 3;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const int v = (acc[c] + (1 << 21)) >> 22;
-            o[c] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
-        }
+        resize_u8_pixel(src + b * sh * (long)sw * 3, sh, sw, sw, dy, dx, scale_x, scale_y, dst + i * 3);
+    }
+}
+
+// The same per image of a ragged bucket: image b is the top-left (h_b, w_b) corner of its slot, on both sides; threads cover
+// the destination SLOTS and those outside their image's corner write nothing.  sizes: DEVICE int[2][B] heights then widths.
+__global__ __launch_bounds__(256) void k_resize_u8_ragged(const unsigned char *__restrict__ src, unsigned char *__restrict__ dst,
+                                                          int B, int src_slot_h, int src_slot_w, int dst_slot_h, int dst_slot_w,
+                                                          const int *__restrict__ src_sizes, const int *__restrict__ dst_sizes,
+                                                          double scale_x, double scale_y) {
+    const long total = (long)B * dst_slot_h * dst_slot_w;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int dx = (int)(i % dst_slot_w);
+        long t = i / dst_slot_w;
+        const int dy = (int)(t % dst_slot_h);
+        const long b = t / dst_slot_h;
+        if (dy >= dst_sizes[b] || dx >= dst_sizes[B + b]) continue;
+        const int sh = min(src_sizes[b], src_slot_h), sw = min(src_sizes[B + b], src_slot_w);   // never past the slot
+        if (sh <= 0 || sw <= 0) continue;
+        resize_u8_pixel(src + b * src_slot_h * (long)src_slot_w * 3, sh, sw, src_slot_w, dy, dx, scale_x, scale_y, dst + i * 3);
     }
 }
 }  // namespace
@@ -767,5 +792,18 @@ extern "C" int pp_resize_u8_cubic(const void *src, void *dst, int batch, int sh,
     hipLaunchKernelGGL(k_resize_u8, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const unsigned char *>(src), static_cast<unsigned char *>(dst), batch, sh, sw, dh, dw, scale_x,
                        scale_y);
+    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
+}
+
+extern "C" int pp_resize_u8_cubic_ragged(const void *src, void *dst, int batch, int src_slot_h, int src_slot_w, int dst_slot_h,
+                                         int dst_slot_w, const int *src_sizes_dev, const int *dst_sizes_dev, double scale_x,
+                                         double scale_y, void *stream) {
+    if (!src || !dst || src == dst || !src_sizes_dev || !dst_sizes_dev || batch <= 0 || src_slot_h <= 0 || src_slot_w <= 0 ||
+        dst_slot_h <= 0 || dst_slot_w <= 0)
+        return PP_ERR_BAD_ARG;
+    const long total = (long)batch * dst_slot_h * dst_slot_w;
+    hipLaunchKernelGGL(k_resize_u8_ragged, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const unsigned char *>(src), static_cast<unsigned char *>(dst), batch, src_slot_h, src_slot_w,
+                       dst_slot_h, dst_slot_w, src_sizes_dev, dst_sizes_dev, scale_x, scale_y);
     return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
 }

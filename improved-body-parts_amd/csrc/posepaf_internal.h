@@ -79,6 +79,10 @@ hipError_t launch_flip_average_planar(const void *net, int dtype, int batch, int
 hipError_t launch_accumulate_scales(int n_scales, const void *const *nets, int dtype, int batch, const int *hs, const int *ws,
                                     int flip, const int *pad_down, const int *pad_right, int img_h, int img_w, double *heat_acc,
                                     double *paf_acc, hipStream_t stream);
+// ragged bucket: sizes / pads HOST (checks, grid, LDS caps), sizes_dev int[2][batch], pads_dev int[n_scales][2][batch]
+hipError_t launch_accumulate_scales_ragged(int n_scales, const void *const *nets, int dtype, int batch, const int *hs, const int *ws,
+                                           int flip, const int *sizes, const int *sizes_dev, const int *pads, const int *pads_dev,
+                                           long slot_area, double *heat_acc, double *paf_acc, hipStream_t stream);
 hipError_t launch_accumulate_scales_affine(int n_scales, const void *const *nets, int dtype, int batch, const int *hs, const int *ws,
                                            int flip, const int *pad_down, const int *pad_right, const double *const *m_inv,
                                            int img_h, int img_w, double *heat_acc, double *paf_acc, hipStream_t stream);
@@ -86,7 +90,8 @@ hipError_t launch_warp_affine_f32(const float *src, float *dst, long n, int h, i
                                   hipStream_t stream);
 hipError_t launch_fullres(int batch, int H, int W, float thre1, int maxp, int cap, int img_height, const double *heat_acc,
                           const double *paf_acc, unsigned char *mask_scratch, void *peaks64, int *counts, void *conns,
-                          int *conn_counts, unsigned *status, pp_record *records, const pp_test_cfg *cfg, hipStream_t stream);
+                          int *conn_counts, unsigned *status, pp_record *records, const pp_test_cfg *cfg, hipStream_t stream,
+                          const int *sizes_dev = nullptr, long slot_area = 0);
 
 }  // namespace pp
 #endif

@@ -2633,29 +2633,51 @@ __device__ __forceinline__ void accumulate_warped_entry(const AccScaleWarp &S, c
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_accumulate_scales(const AccParams P) {
+// A ragged bucket (pp_original_accumulate_all_ragged): images of different sizes that share every scale's padded shape.
+// sizes: DEVICE int[2][batch] heights then widths; pads: DEVICE int[n][2][batch], per scale pad_down then pad_right; plane
+// (b, c) of an accumulator starts at (b * C + c) * slot_area and is dense (row length = the image's own width).
+struct AccRagged {
+    const int *sizes, *pads;
+    long slot_area;
+};
+// The body of both instances.  RAGGED: the image's extent and each scale's crop come from the device arrays, and (ch, cw,
+// identity, sx, sy) are formed by the expressions launch_accumulate_scales evaluates on the host (the same two IEEE double
+// divisions), so an image gets the bits it gets alone.  The grid is sized for the largest image: a workgroup whose tile lies
+// outside its own image returns, as a whole, before the first barrier.
+template <typename T, bool RAGGED>
+__device__ __forceinline__ void accumulate_scales_body(const AccParams &P, const AccRagged &R) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     float *sU = reinterpret_cast<float *>(lds_raw);
     float *sA = sU + P.u_cap;
-    const int tiles_x = (P.img_w + kAccTile - 1) / kAccTile;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int c = blockIdx.y, b = blockIdx.z;
+    const int img_h = RAGGED ? R.sizes[b] : P.img_h, img_w = RAGGED ? R.sizes[gridDim.z + b] : P.img_w;
+    const int tiles_x = (img_w + kAccTile - 1) / kAccTile;
+    if (RAGGED && (int)blockIdx.x >= tiles_x * ((img_h + kAccTile - 1) / kAccTile)) return;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int oy0 = ty * kAccTile, ox0 = tx * kAccTile;
-    const int oy1 = min(oy0 + kAccTile, P.img_h), ox1 = min(ox0 + kAccTile, P.img_w);
+    const int oy1 = min(oy0 + kAccTile, img_h), ox1 = min(ox0 + kAccTile, img_w);
     const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;   // this thread's output pixels: (oy0 + ly + 8 k, ox0 + lx)
     const int ns = P.flip ? 2 : 1;
     const int cf = c < PP_NUM_LIMB ? d_flip_paf_ord[c] : PP_NUM_LIMB + d_flip_heat_ord[c - PP_NUM_LIMB];
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int si = 0; si < P.n; si++) {
         const AccScale &S = P.s[si];
+        int ch = S.ch, cw = S.cw, identity = S.identity;
+        double scx = S.sx, scy = S.sy;
+        if (RAGGED) {
+            ch = 4 * S.h - R.pads[(si * 2) * gridDim.z + b];
+            cw = 4 * S.w - R.pads[(si * 2 + 1) * gridDim.z + b];
+            identity = (ch == img_h && cw == img_w) ? 1 : 0;
+            scx = 1.0 / ((double)img_w / (double)cw);
+            scy = 1.0 / ((double)img_h / (double)ch);
+        }
         // ---- rows / columns of U the tile's taps reach, then rows / columns of A those reach (clamped like the taps are)
         int ur0, ur1, uc0, uc1;
-        if (S.identity) {
+        if (identity) {
             ur0 = oy0, ur1 = oy1 - 1, uc0 = ox0, uc1 = ox1 - 1;
         } else {
-            ur0 = clampi(src_floor(oy0, S.sy) - 1, 0, S.ch - 1), ur1 = clampi(src_floor(oy1 - 1, S.sy) + 2, 0, S.ch - 1);
-            uc0 = clampi(src_floor(ox0, S.sx) - 1, 0, S.cw - 1), uc1 = clampi(src_floor(ox1 - 1, S.sx) + 2, 0, S.cw - 1);
+            ur0 = clampi(src_floor(oy0, scy) - 1, 0, ch - 1), ur1 = clampi(src_floor(oy1 - 1, scy) + 2, 0, ch - 1);
+            uc0 = clampi(src_floor(ox0, scx) - 1, 0, cw - 1), uc1 = clampi(src_floor(ox1 - 1, scx) + 2, 0, cw - 1);
         }
         const int un = ur1 - ur0 + 1, um = uc1 - uc0 + 1;
         const int ar0 = clampi(src_floor(ur0, 0.25) - 1, 0, S.h - 1), ar1 = clampi(src_floor(ur1, 0.25) + 2, 0, S.h - 1);
@@ -2716,24 +2738,24 @@ __global__ __launch_bounds__(256) void k_accumulate_scales(const AccParams P) {
             const int dy = oy0 + ly + 8 * k, dx = ox0 + lx;
             if (dy < oy1 && dx < ox1) {
                 float v;
-                if (S.identity) {
+                if (identity) {
                     v = sU[(dy - ur0) * um + (dx - uc0)];
                 } else {
-                    float fx = (float)(((double)dx + 0.5) * S.sx - 0.5);
+                    float fx = (float)(((double)dx + 0.5) * scx - 0.5);
                     const int sx = (int)floorf(fx);
                     fx = __fadd_rn(fx, -(float)sx);
-                    float fy = (float)(((double)dy + 0.5) * S.sy - 0.5);
+                    float fy = (float)(((double)dy + 0.5) * scy - 0.5);
                     const int sy = (int)floorf(fy);
                     fy = __fadd_rn(fy, -(float)sy);
                     float ca[4], cb[4];
                     cubic_coeffs(fx, ca);
                     cubic_coeffs(fy, cb);
-                    const int x0 = clampi(sx - 1, 0, S.cw - 1) - uc0, x1 = clampi(sx, 0, S.cw - 1) - uc0,
-                              x2 = clampi(sx + 1, 0, S.cw - 1) - uc0, x3 = clampi(sx + 2, 0, S.cw - 1) - uc0;
+                    const int x0 = clampi(sx - 1, 0, cw - 1) - uc0, x1 = clampi(sx, 0, cw - 1) - uc0,
+                              x2 = clampi(sx + 1, 0, cw - 1) - uc0, x3 = clampi(sx + 2, 0, cw - 1) - uc0;
                     float hrow[4];
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
-                        const float *row = sU + (clampi(sy - 1 + r, 0, S.ch - 1) - ur0) * um;
+                        const float *row = sU + (clampi(sy - 1 + r, 0, ch - 1) - ur0) * um;
                         float hv = __fmul_rn(row[x0], ca[0]);
                         hv = __fadd_rn(hv, __fmul_rn(row[x1], ca[1]));
                         hv = __fadd_rn(hv, __fmul_rn(row[x2], ca[2]));
@@ -2750,13 +2772,23 @@ __global__ __launch_bounds__(256) void k_accumulate_scales(const AccParams P) {
         }
         __syncthreads();   // the tiles are rewritten by the next scale
     }
-    double *D = c < PP_NUM_LIMB ? P.paf_acc + ((long)b * PP_NUM_LIMB + c) * P.img_h * P.img_w
-                                : P.heat_acc + ((long)b * PP_NUM_HEAT + (c - PP_NUM_LIMB)) * P.img_h * P.img_w;
+    const long plane = RAGGED ? R.slot_area : (long)img_h * img_w;
+    double *D = c < PP_NUM_LIMB ? P.paf_acc + ((long)b * PP_NUM_LIMB + c) * plane
+                                : P.heat_acc + ((long)b * PP_NUM_HEAT + (c - PP_NUM_LIMB)) * plane;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int dy = oy0 + ly + 8 * k, dx = ox0 + lx;
-        if (dy < oy1 && dx < ox1) D[(long)dy * P.img_w + dx] = acc[k];
+        if (dy < oy1 && dx < ox1) D[(long)dy * img_w + dx] = acc[k];
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_accumulate_scales(const AccParams P) {
+    accumulate_scales_body<T, false>(P, AccRagged{nullptr, nullptr, 0});
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_accumulate_scales_ragged(const AccParams P, const AccRagged R) {
+    accumulate_scales_body<T, true>(P, R);
 }
 
 // The same with rotated entries (pp_original_accumulate_all_affine); LDS: U tile / pre-image box, A tile, W region.  Entries
@@ -3191,6 +3223,54 @@ hipError_t launch_accumulate_scales(int n_scales, const void *const *nets, int d
     return hipGetLastError();
 }
 
+// The same launch for a ragged bucket.  The host arrays serve the checks, the grid (the largest tile count of any image) and the
+// LDS capacities (the worst image of each scale, by the expressions above); the kernel reads the device copies.
+hipError_t launch_accumulate_scales_ragged(int n_scales, const void *const *nets, int dtype, int batch, const int *hs, const int *ws,
+                                           int flip, const int *sizes, const int *sizes_dev, const int *pads, const int *pads_dev,
+                                           long slot_area, double *heat_acc, double *paf_acc, hipStream_t stream) {
+    if (n_scales < 1 || n_scales > kAccMaxScales) return hipErrorInvalidValue;
+    AccParams P;
+    P.n = n_scales;
+    P.flip = flip;
+    P.img_h = P.img_w = 0;   // per image, from sizes_dev
+    P.n_div = (float)n_scales;
+    P.heat_acc = heat_acc;
+    P.paf_acc = paf_acc;
+    int umax = 0, amax = 0, tiles = 0;
+    for (int b = 0; b < batch; b++) {
+        const int t = ((sizes[batch + b] + kAccTile - 1) / kAccTile) * ((sizes[b] + kAccTile - 1) / kAccTile);
+        tiles = t > tiles ? t : tiles;
+    }
+    for (int i = 0; i < n_scales; i++) {
+        AccScale &S = P.s[i];
+        S.net = nets[i];
+        S.h = hs[i];
+        S.w = ws[i];
+        S.ch = S.cw = S.identity = 0;   // per image, from pads_dev
+        S.sx = S.sy = 0.0;
+        for (int b = 0; b < batch; b++) {
+            const int img_h = sizes[b], img_w = sizes[batch + b];
+            const int ch = 4 * hs[i] - pads[(i * 2) * batch + b], cw = 4 * ws[i] - pads[(i * 2 + 1) * batch + b];
+            if (ch <= 0 || cw <= 0) return hipErrorInvalidValue;
+            const int identity = (ch == img_h && cw == img_w) ? 1 : 0;
+            const double sx = 1.0 / ((double)img_w / (double)cw), sy = 1.0 / ((double)img_h / (double)ch);
+            const int ur = identity ? kAccTile : (int)(kAccTile * sy) + 6, uc = identity ? kAccTile : (int)(kAccTile * sx) + 6;
+            const int ar = ur / 4 + 6, ac = uc / 4 + 6;
+            umax = ur * uc > umax ? ur * uc : umax;
+            amax = ar * ac > amax ? ar * ac : amax;
+        }
+    }
+    P.u_cap = umax;
+    P.a_cap = amax;
+    const size_t lds = ((size_t)umax + amax) * sizeof(float);
+    if (lds > 60000) return hipErrorInvalidValue;
+    const AccRagged R{sizes_dev, pads_dev, slot_area};
+    const dim3 grid(tiles, PP_NUM_CH, batch);
+    if (dtype == PP_F16) hipLaunchKernelGGL(k_accumulate_scales_ragged<__half>, grid, dim3(256), lds, stream, P, R);
+    else hipLaunchKernelGGL(k_accumulate_scales_ragged<float>, grid, dim3(256), lds, stream, P, R);
+    return hipGetLastError();
+}
+
 // The rotation search's form: m_inv[i] (HOST, 6 doubles, or NULL = entry i is not rotated).  No rotated entry: the launch above,
 // unchanged.  LDS per rotated entry is bounded on the host from the inverted matrix: the pre-image of the W region (rr x rc)
 // spans |m0| (rc - 1) + |m1| (rr - 1) columns and |m3| (rc - 1) + |m4| (rr - 1) rows of U, plus slack for the fixed-point
@@ -3280,21 +3360,23 @@ hipError_t launch_warp_affine_f32(const float *src, float *dst, long n, int h, i
 
 hipError_t launch_fullres(int batch, int H, int W, float thre1, int maxp, int cap, int img_height, const double *heat_acc,
                           const double *paf_acc, unsigned char *mask_scratch, void *peaks64, int *counts, void *conns,
-                          int *conn_counts, unsigned *status, pp_record *records, const pp_test_cfg *cfg, hipStream_t stream) {
+                          int *conn_counts, unsigned *status, pp_record *records, const pp_test_cfg *cfg, hipStream_t stream,
+                          const int *sizes_dev, long slot_area) {
     if (cfg_moves_peaks(cfg))
         hipLaunchKernelGGL(k_fullres_peaks_cfg, dim3(PP_NUM_PART, batch), dim3(kThreads), 0, stream, heat_acc, H, W, thre1, maxp,
-                           mask_scratch, static_cast<double4 *>(peaks64), counts, status, make_py_cfg(*cfg));
+                           mask_scratch, static_cast<double4 *>(peaks64), counts, status, sizes_dev, slot_area,
+                           make_py_cfg(*cfg));
     else
         hipLaunchKernelGGL(k_fullres_peaks, dim3(PP_NUM_PART, batch), dim3(kThreads), 0, stream, heat_acc, H, W, thre1, maxp,
-                           mask_scratch, static_cast<double4 *>(peaks64), counts, status);
+                           mask_scratch, static_cast<double4 *>(peaks64), counts, status, sizes_dev, slot_area);
     if (cfg_moves_limb(cfg))
         hipLaunchKernelGGL(k_limb_connect_py_fullres_cfg, dim3(PP_NUM_LIMB, batch), dim3(kThreads), limb_lds_bytes_py(maxp, cap),
                            stream, paf_acc, H, W, maxp, cap, img_height, static_cast<const double4 *>(peaks64), counts,
-                           static_cast<double4 *>(conns), conn_counts, status, make_py_cfg(*cfg));
+                           static_cast<double4 *>(conns), conn_counts, status, sizes_dev, slot_area, make_py_cfg(*cfg));
     else
         hipLaunchKernelGGL(k_limb_connect_py_fullres, dim3(PP_NUM_LIMB, batch), dim3(kThreads), limb_lds_bytes_py(maxp, cap), stream,
                            paf_acc, H, W, maxp, cap, img_height, static_cast<const double4 *>(peaks64), counts,
-                           static_cast<double4 *>(conns), conn_counts, status);
+                           static_cast<double4 *>(conns), conn_counts, status, sizes_dev, slot_area);
     if (cfg_moves_assembly(cfg))
         hipLaunchKernelGGL(k_assemble_py_cfg<double4>, dim3(batch), dim3(64), lds_bytes_assemble_py(maxp), stream, maxp, 0,
                            static_cast<const double4 *>(peaks64), counts, static_cast<const double4 *>(conns), conn_counts, status,

@@ -530,14 +530,20 @@ __global__ __launch_bounds__(64) void PP_PYK(k_assemble_py)(int maxp, int explic
 __global__ __launch_bounds__(kThreads) void PP_PYK(k_fullres_peaks)(const double *__restrict__ heat_acc, int H, int W, float thre,
                                                             int maxp, unsigned char *__restrict__ mask_scratch,
                                                             double4 *__restrict__ peaks, int *__restrict__ counts,
-                                                            unsigned *__restrict__ status PP_PY_CFG_PARAM) {
+                                                            unsigned *__restrict__ status, const int *__restrict__ sizes,
+                                                            long slot_area PP_PY_CFG_PARAM) {
     __shared__ int s_wsum[kWaves];
     __shared__ int s_pk[PP_MAX_PEAKS_PER_PART_LIMIT];
     const int part = blockIdx.x, img = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (sizes) {  // ragged bucket: this image's own extent, its planes dense at the head of slots of slot_area elements
+        H = sizes[img];
+        W = sizes[gridDim.y + img];
+    }
     const long npix = (long)H * W;
-    const double *M = heat_acc + ((long)img * PP_NUM_HEAT + part) * npix;
-    unsigned char *mask = mask_scratch + ((long)img * PP_NUM_PART + part) * npix;
+    const long plane = sizes ? slot_area : npix;
+    const double *M = heat_acc + ((long)img * PP_NUM_HEAT + part) * plane;
+    unsigned char *mask = mask_scratch + ((long)img * PP_NUM_PART + part) * plane;
     auto val = [&](long i) -> float { return (float)M[i]; };
     for (long i = threadIdx.x; i < npix; i += kThreads) {
         const float v = val(i);
@@ -662,9 +668,17 @@ __global__ __launch_bounds__(kThreads) void PP_PYK(k_limb_connect_py_fullres)(co
                                                                       int cap, int img_height,
                                                                       const double4 *__restrict__ peaks,
                                                                       const int *__restrict__ counts, double4 *__restrict__ conns,
-                                                                      int *__restrict__ conn_counts, unsigned *__restrict__ status PP_PY_CFG_PARAM) {
+                                                                      int *__restrict__ conn_counts, unsigned *__restrict__ status,
+                                                                      const int *__restrict__ sizes, long slot_area PP_PY_CFG_PARAM) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int limb = blockIdx.x, img = blockIdx.y;
+    long plane = (long)H * W;
+    if (sizes) {  // ragged bucket: the sampler clamps to this image's own extent; img_h of find_connections is its height
+        H = sizes[img];
+        W = sizes[gridDim.y + img];
+        img_height = H;
+        plane = slot_area;
+    }
     const int pa = d_limb_pairs[limb][0], pb = d_limb_pairs[limb][1];
     int nA = counts[img * PP_NUM_PART + pa], nB = counts[img * PP_NUM_PART + pb];
     nA = nA < maxp ? nA : maxp;
@@ -697,7 +711,7 @@ __global__ __launch_bounds__(kThreads) void PP_PYK(k_limb_connect_py_fullres)(co
         L.usedB[i] = 0;
     }
     __syncthreads();
-    GlobalPlanarF64Sampler smp{paf_acc + ((long)img * PP_NUM_LIMB + limb) * (long)H * W, H, W};
+    GlobalPlanarF64Sampler smp{paf_acc + ((long)img * PP_NUM_LIMB + limb) * plane, H, W};
     PP_PYK(connect_limb_py)(smp, L, nA, nB, cap, maxp, img_height, conns + ((long)img * PP_NUM_LIMB + limb) * maxp, cc,
                             status + img * kFlagWords + PP_NUM_PART + limb PP_PY_CFG_ARG);
 }

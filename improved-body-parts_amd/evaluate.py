@@ -7,6 +7,8 @@
     python evaluate.py --synthetic 512 --batch 32 --scales 1.0 --test_cfg thre2=0.05 mid_num=40 remove_recon=1   # original
         path with the reference's test_cfg keys as run-time values (or --config_file PATH: the [param] section of an INI file)
     python evaluate.py --run_refactor --run_cpp --synthetic 256 --render_dir out/    # + every image with its skeletons drawn
+    python evaluate.py --synthetic 256 --batch 32 --scales 0.5 1.0 1.5 --sizes 512x480,480x512,500x475   # original path: sizes
+        that pad alike at every scale share one ragged bucket (POSEPAF_ORIGINAL_BUCKETS=exact: group by exact size instead)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --synthetic 5000 ...
 
 What is kept from the reference: the flags --run_refactor / --run_cpp (:53-54; --run_cpp selects the C++ pafprocess rules --
@@ -348,15 +350,22 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
 
 def run_original(a, src, mine, model, post, dev):
     """evaluate.py:81-89 without --run_refactor: predict + find_peaks + find_connections + find_humans at image resolution,
-    with a real scale search.  Accumulators live at image resolution, so images are bucketed by exact size; per batch the images
-    are decoded by a thread pool into a pinned buffer (uploaded while the previous batch computes), every scale runs
+    with a real scale search.  Images are grouped by posepaf.original_path.bucket_key: those whose scaled sizes pad to one shape
+    at EVERY scale share the forwards.  A group of one size runs the equal-size kernels; a mixed group is a ragged bucket: the
+    images sit in the corners of equal slots, every image is resized / padded / cropped / searched at its own size
+    (pp_resize_u8_cubic_ragged, pp_preprocess_u8_ragged, pp_original_accumulate_all_ragged, pp_original_finish_ragged) and
+    comes out bit for bit as it does alone.  POSEPAF_ORIGINAL_BUCKETS=exact groups by exact size instead (A/B runs), and so
+    does a --rotation_search with a non-zero angle (the warped accumulation has no ragged form).  Per batch the images are
+    decoded by a thread pool into a pinned buffer (uploaded while the previous batch computes), every scale runs
     resize -> pad / normalise / mirror -> forward, and ALL scales are accumulated by one launch (pp_original_accumulate_all).
     With --rotation_search every (scale, angle) entry is one more forward: the padded input is rotated by the pre-processing
     kernel and the entry's x4 maps are warped back inside the same launch (pp_original_accumulate_all_affine).
-    Synthetic runs take their scenes from a device-resident bank per (scale, angle) (64 scenes), like the refactored path;
-    a rotated entry's scenes are rendered at the rotated positions (synth.make_scene_at_scales)."""
+    Synthetic runs take their scenes from a device-resident bank per (size, scale, angle) (64 scenes), like the refactored
+    path; a rotated entry's scenes are rendered at the rotated positions (synth.make_scene_at_scales).  The banks of a ragged
+    bucket's sizes have equal map shapes and are concatenated once per bucket."""
     from concurrent.futures import ThreadPoolExecutor
-    from posepaf.original_path import OriginalPathProcessor, resize_images_u8, scaled_size
+    from posepaf.original_path import (OriginalPathProcessor, RaggedBucket, RaggedUnsupported, group_by_bucket_key,
+                                       preprocess_ragged, resize_images_u8)
     from posepaf.pipeline import preprocess_batch
     from posepaf.rotation import input_and_map_inverses
     B, scales = a.batch, a.scales or [1.0]
@@ -367,32 +376,60 @@ def run_original(a, src, mine, model, post, dev):
         post.set_test_cfg(a.test_cfg_dict)
         thre1 = a.test_cfg_dict["thre1"]
     shapes = [src.shape(int(i)) for i in mine]
-    groups = {}
-    for k, hw in enumerate(shapes):
-        groups.setdefault(hw, []).append(k)
+    exact = os.environ.get("POSEPAF_ORIGINAL_BUCKETS", "") == "exact" or any(ang != 0.0 for ang in angles)
+    groups = group_by_bucket_key(shapes, scales, exact)
     local = torch.zeros((max(len(mine), 1), RECORD_BYTES), dtype=torch.uint8, device=dev)
     scale = torch.tensor(1e-3, dtype=torch.float16, device=dev)
     workers = a.workers or max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 8))
     pool = ThreadPoolExecutor(max_workers=workers)
     banks = {}
-    with torch.no_grad():   # untimed set-up per image size: convolution shapes of every scale, scene banks
-        for (H, W) in groups:
-            warm = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=dev)
-            for sc in scales:
-                x = preprocess_batch(resize_images_u8(warm, float(sc)), True, torch.float16)
-                model(x)
-                if src.has_scenes:
-                    fh, fw = x.shape[1] // 4, x.shape[2] // 4
-                    for ang in angles:
-                        entry = (fh, fw, float(sc)) if ang == 0.0 else (fh, fw, float(sc), ang)
-                        arr = np.stack([synth.make_scene_at_scales(src.n_people(s_), 20_000 + s_, [entry], img=H)[0][0]
-                                        for s_ in range(SCENE_BANK)])
-                        banks[(H, W, float(sc), ang)] = torch.from_numpy(arr).to(dev)
+
+    def scene_bank(H, W, fh, fw, sc, ang):
+        entry = (fh, fw, float(sc)) if ang == 0.0 else (fh, fw, float(sc), ang)
+        return np.stack([synth.make_scene_at_scales(src.n_people(s_), 20_000 + s_, [entry], img=H)[0][0]
+                         for s_ in range(SCENE_BANK)])
+
+    def setup_exact(H, W):   # convolution shapes of every scale, scene banks of one image size
+        if (H, W) in banks:
+            return
+        banks[(H, W)] = True
+        warm = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=dev)
+        for sc in scales:
+            x = preprocess_batch(resize_images_u8(warm, float(sc)), True, torch.float16)
+            model(x)
+            if src.has_scenes:
+                fh, fw = x.shape[1] // 4, x.shape[2] // 4
+                for ang in angles:
+                    banks[(H, W, float(sc), ang)] = torch.from_numpy(scene_bank(H, W, fh, fw, sc, ang)).to(dev)
+
+    def setup_ragged(key, members):   # one warm-up forward per scale for the whole bucket; its sizes' banks, concatenated
+        sizes = sorted({shapes[k] for k in members})
+        for sc, (ph, pw) in zip(scales, key):
+            model(torch.zeros((2 * B, ph, pw, 3), dtype=torch.float16, device=dev))
+            if src.has_scenes:
+                banks[(key, float(sc))] = torch.from_numpy(np.concatenate(
+                    [scene_bank(H, W, ph // 4, pw // 4, sc, 0.0) for (H, W) in sizes])).to(dev)
+        banks[(key, "sizes")] = {hw: n for n, hw in enumerate(sizes)}
+
+    with torch.no_grad():   # untimed set-up per group
+        for key, members, ragged in groups:
+            if ragged:
+                setup_ragged(key, members)
+            else:
+                setup_exact(*shapes[members[0]])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     copy_stream = torch.cuda.Stream(device=dev)
-    for (H, W), members in groups.items():
-        proc = OriginalPathProcessor(post, H, W, B)
+
+    def run_group(members, ragged_key=None):
+        """one group through the double-buffered loop.  ragged_key None: every image is (H, W), the equal-size kernels."""
+        if ragged_key is None:
+            H, W = shapes[members[0]]
+            proc = OriginalPathProcessor(post, H, W, B)
+        else:   # slots that hold the bucket's largest image and have the padded shape of scale 1
+            H, W = padded_shape(max(shapes[k][0] for k in members), max(shapes[k][1] for k in members))
+            proc = OriginalPathProcessor(post, None, None, B, slot_area=max(shapes[k][0] * shapes[k][1] for k in members))
+            size_index = banks[(ragged_key, "sizes")]
         pinned = [torch.zeros((B, H, W, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
         staged = [torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
         events = [None, None]
@@ -407,7 +444,11 @@ def run_original(a, src, mine, model, post, dev):
             view = pinned[k].numpy()
 
             def put(t):
-                view[t[0]] = src.load(int(mine[t[1]]))
+                if ragged_key is None:
+                    view[t[0]] = src.load(int(mine[t[1]]))
+                else:
+                    h, w = shapes[t[1]]
+                    view[t[0], :h, :w] = src.load(int(mine[t[1]]))
             list(pool.map(put, enumerate(batches[j])))
             with torch.cuda.stream(copy_stream):
                 staged[k].copy_(pinned[k], non_blocking=True)
@@ -424,27 +465,57 @@ def run_original(a, src, mine, model, post, dev):
             dev_imgs = staged[k]
             slots = torch.tensor([src.scene_slot(i) for i in idx] + [0] * (B - n), dtype=torch.int64, device=dev) if src.has_scenes else None
             with torch.no_grad():
-                proc.reset()
-                for sc in scales:
-                    scaled = resize_images_u8(dev_imgs, float(sc))
-                    sh, sw = scaled.shape[1:3]
-                    for ang in angles:
-                        m_in, m_rev = input_and_map_inverses(*padded_shape(sh, sw), ang)
-                        x = preprocess_batch(scaled, True, torch.float16, m_inv=m_in)
-                        ph, pw = x.shape[1:3]
-                        maps = model(x).contiguous().view(B, 2, 50, ph // 4, pw // 4)
-                        if src.has_scenes:   # the same synthetic people, rendered at this scale (and rotation)
-                            maps = torch.addcmul(banks[(H, W, float(sc), ang)].index_select(0, slots), maps, scale)
-                        proc.accumulate(maps, ph - sh, pw - sw, n_div, m_inv=m_rev)
+                if ragged_key is None:
+                    proc.reset()
+                    for sc in scales:
+                        scaled = resize_images_u8(dev_imgs, float(sc))
+                        sh, sw = scaled.shape[1:3]
+                        for ang in angles:
+                            m_in, m_rev = input_and_map_inverses(*padded_shape(sh, sw), ang)
+                            x = preprocess_batch(scaled, True, torch.float16, m_inv=m_in)
+                            ph, pw = x.shape[1:3]
+                            maps = model(x).contiguous().view(B, 2, 50, ph // 4, pw // 4)
+                            if src.has_scenes:   # the same synthetic people, rendered at this scale (and rotation)
+                                maps = torch.addcmul(banks[(H, W, float(sc), ang)].index_select(0, slots), maps, scale)
+                            proc.accumulate(maps, ph - sh, pw - sw, n_div, m_inv=m_rev)
+                else:   # a short last batch repeats its first image's size in the unused slots (their records are dropped)
+                    sizes = [shapes[q] for q in loc] + [shapes[loc[0]]] * (B - n)
+                    rg = RaggedBucket(sizes, scales, dev)
+                    if src.has_scenes:   # each image's scene comes from the bank of its own (H, W, scale)
+                        slots = slots + torch.tensor([size_index[hw] * SCENE_BANK for hw in sizes], dtype=torch.int64, device=dev)
+                    proc.reset(rg)
+                    for i, sc in enumerate(scales):
+                        scaled = resize_images_u8(dev_imgs, float(sc), ragged=rg)
+                        ph, pw = scaled.shape[1:3]
+                        maps = model(preprocess_ragged(scaled, rg.dev[1 + i], torch.float16)).contiguous().view(B, 2, 50, ph // 4, pw // 4)
+                        if src.has_scenes:
+                            maps = torch.addcmul(banks[(ragged_key, float(sc))].index_select(0, slots), maps, scale)
+                        proc.accumulate(maps, *rg.pads(i), n_div)
                 rec = proc.finish(B, thre1)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
             events[k][1] = done
             local.index_copy_(0, torch.tensor(loc, dtype=torch.int64, device=dev), rec.view(B, RECORD_BYTES)[:n])
             stage(j + 1)                            # the next batch is decoded and uploaded while this one computes
+
+    n_ragged = 0
+    for key, members, ragged in groups:
+        if not ragged:
+            run_group(members)
+            continue
+        try:
+            run_group(members, key)
+            n_ragged += 1
+        except RaggedUnsupported:   # raised by the bucket's first batch, before any record: its images by exact size instead
+            torch.cuda.synchronize()
+            for _, sub, _ in group_by_bucket_key([shapes[k] for k in members], scales, exact=True):
+                with torch.no_grad():
+                    setup_exact(*shapes[members[sub[0]]])
+                run_group([members[q] for q in sub])
     torch.cuda.synchronize()
     pool.shutdown(wait=False)
-    info = {"launch": "eager", "scales": scales, "decode_threads": workers}
+    info = {"launch": "eager", "scales": scales, "decode_threads": workers,
+            "original_buckets": {"groups": len(groups), "ragged": n_ragged}}
     if a.rotation_search is not None:
         info["rotation_search"] = angles
     info["test_cfg"] = post.test_cfg      # the configuration in force, read back from the context

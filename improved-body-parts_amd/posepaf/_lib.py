@@ -34,7 +34,8 @@ EXPORTS = [
     "pp_get_num_humans", "pp_get_part_peak_id", "pp_get_score", "pp_get_part_x", "pp_get_part_y",
     "pp_get_part_score", "pp_get_status", "pp_py_find_connections_host", "pp_py_find_humans_host", "pp_original_accumulate", "pp_original_accumulate_all", "pp_original_finish",
     "pp_preprocess_u8_affine", "pp_original_accumulate_affine", "pp_original_accumulate_all_affine", "pp_warp_affine_f32",
-    "pp_resize_u8_cubic", "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
+    "pp_resize_u8_cubic", "pp_resize_u8_cubic_ragged", "pp_original_accumulate_all_ragged", "pp_original_finish_ragged",
+    "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
     "pp_set_map_residency", "pp_map_residency", "pp_map_workspace_bytes", "pp_time_map_prepass", "pp_draw_humans_u8",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
@@ -154,6 +155,10 @@ def load():
     L.pp_warp_affine_f32.argtypes = [vp, vp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, dp, vp]
     L.pp_original_finish.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]
     L.pp_resize_u8_cubic.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp]
+    L.pp_resize_u8_cubic_ragged.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double, vp]
+    L.pp_original_accumulate_all_ragged.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int, ip, ip, C.c_int, ip, vp, ip, vp,
+                                                    C.c_long, vp, vp, vp]
+    L.pp_original_finish_ragged.argtypes = [vp, C.c_int, ip, vp, C.c_long, C.c_float, vp, vp, vp, vp, vp, vp]
     L.pp_get_num_humans.argtypes = [vp]
     L.pp_get_part_peak_id.argtypes = [vp, C.c_int, C.c_int]
     L.pp_get_score.argtypes = [vp, C.c_int]

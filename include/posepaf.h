@@ -430,6 +430,34 @@ PP_API int pp_original_finish(pp_ctx *ctx, int batch, int img_h, int img_w, floa
                               void *stream);
 PP_API int pp_resize_u8_cubic(const void *src, void *dst, int batch, int sh, int sw, int dh, int dw, double scale_x,
                               double scale_y, void *stream);
+/* The original path for a RAGGED bucket: images of different sizes whose scaled sizes pad to one shape at every scale, so that one
+ * forward per scale serves them all (posepaf/original_path.py bucket_key).  Every image comes out bit for bit as it does alone
+ * through the entries above.  Layout:
+ *   uint8 images  (batch, slot_h, slot_w, 3), image b in the top-left (h_b, w_b) corner of its slot (as pp_preprocess_u8_ragged
+ *                 reads them); the rest of a slot is never read and, on output, never written;
+ *   sizes         int[2][batch], heights then widths, as a DEVICE array the kernels read and as a HOST array with the SAME values
+ *                 for the argument checks, the grid and the LDS capacities;
+ *   heat_acc      double[batch][20][slot_area], paf_acc double[batch][30][slot_area], mask_scratch uchar[batch][18][slot_area]:
+ *                 plane (b, c) starts at (b * C + c) * slot_area and holds h_b x w_b values row-major with row length w_b (no
+ *                 pitch); the tail of a slot is never read or written; slot_area >= h_b * w_b for every image.
+ * pp_resize_u8_cubic_ragged: per image pp_resize_u8_cubic of the source corner into the destination corner; dst_sizes_dev holds
+ *   what cv2.resize gives each image (round half to even, computed by the host); scale_x = scale_y = 1 / scale for all of them.
+ * pp_original_accumulate_all_ragged: pp_original_accumulate_all with a per-image image size and crop.  pads: int[n_scales][2]
+ *   [batch], per scale pad_down then pad_right of every image, HOST and DEVICE.  PP_ERR_UNSUPPORTED where
+ *   pp_original_accumulate_all answers it for one of the images: run that bucket as exact-size groups then.  No allocation, no
+ *   host synchronisation.
+ * pp_original_finish_ragged: pp_original_finish with each image's own extent for the NMS borders, the refine_centroid window
+ *   and the limb sampler's clamp, and its own height as find_connections' img_h. */
+PP_API int pp_resize_u8_cubic_ragged(const void *src, void *dst, int batch, int src_slot_h, int src_slot_w, int dst_slot_h,
+                                     int dst_slot_w, const int *src_sizes_dev, const int *dst_sizes_dev, double scale_x,
+                                     double scale_y, void *stream);
+PP_API int pp_original_accumulate_all_ragged(pp_ctx *ctx, int batch, int n_scales, const void *const *net_out_dev, int dtype,
+                                             const int *h, const int *w, int flip, const int *sizes, const int *sizes_dev,
+                                             const int *pads, const int *pads_dev, long slot_area, double *heat_acc,
+                                             double *paf_acc, void *stream);
+PP_API int pp_original_finish_ragged(pp_ctx *ctx, int batch, const int *sizes, const int *sizes_dev, long slot_area, float thre1,
+                                     const double *heat_acc, const double *paf_acc, unsigned char *mask_scratch,
+                                     void *peaks64_scratch, pp_record *records_dev, void *stream);
 
 /* ---------------------------------------------------------------- run-time test configuration (Python rules)
  * The matching rules the reference's Python post-processing reads from test_cfg (utils/config:16-27,
