@@ -700,7 +700,9 @@ extern "C" int pp_flip_average(const void *net_out_dev, int dtype, int batch, in
 
 // ------------------------------------------------------------------------------------------------ A0, scale != 1
 // cv2.resize(image, fx=fy=scale, INTER_CUBIC) on the uint8 image (utils/parse_skeletons.py:204): OpenCV's fixed-point
-// bicubic restated (see oracle/posepaf_oracle.c, orc_resize_cubic_u8; parity unpinned).  One thread per output pixel.
+// bicubic restated (see oracle/posepaf_oracle.c, orc_resize_cubic_u8).  Every pixel is within one count of the bicubic in
+// real arithmetic (tests/test_gpu_cubic.py); OpenCV's own last bits are unverified (OpenCV absent).  One thread per output
+// pixel.
 namespace {
 __device__ __forceinline__ void cubic_coeffs_i(float x, int c[4]) {
     const float A = -0.75f;

@@ -102,7 +102,11 @@ uint16_t orc_f32_to_f16(float f) {
  * requirements.txt:58-59): interpolateCubic with A = -0.75; source coordinate
  * fx = (dx + 0.5) * scale - 0.5, sx = floor(fx); taps sx-1..sx+2 with indices clamped to the source
  * (border replicate); horizontal pass then vertical pass, float32, products summed left to right.
- * Parity UNPINNED: OpenCV is not installed here and the reference has no fixture for it. */
+ * OpenCV is not installed here and the reference has no fixture for it.  PINNED: the algorithm, A, the pixel centres, the
+ * borders, the float coordinate and the x4 phase table -- to an independent float64 statement of Keys' kernel
+ * (tests/cubic_reference.py) and through it to torch's float64 bicubic (tests/test_cubic_reference_cpu.py; float32 rounding
+ * is the only difference, and four plausible wrong algorithms miss the bound by more than 1000x).  NOT pinned: OpenCV's own
+ * last bits (its SIMD / IPP paths). */
 
 void orc_cubic_coeffs(float x, float c[4]) {
     const float A = -0.75f;
@@ -1219,7 +1223,8 @@ int orc_find_peaks_original(const double *heat_acc, int img_h, int img_w, float 
 /* cv2.resize(INTER_CUBIC) on an 8-bit image (predict :204 for scale != 1): OpenCV's fixed-point path restated --
  * coefficients scaled by 2048 and rounded to short, integer horizontal pass, vertical pass (sum + 2^21) >> 22 with
  * saturation (resize.cpp: HResizeCubic<uchar,int,short>, VResizeCubic + FixedPtCast<int,uchar,22>, scalar form; the
- * SSE form of the vertical pass rounds in float and can differ by one count).  PARITY UNPINNED (OpenCV absent). */
+ * SSE form of the vertical pass rounds in float and can differ by one count).  Pinned to real arithmetic within one count
+ * (tests/test_cubic_reference_cpu.py); OpenCV's own last bits are not (OpenCV absent). */
 void orc_resize_cubic_u8(const unsigned char *src, int sh, int sw, int cn, unsigned char *dst, int dh, int dw,
                          double scale_x, double scale_y) {
     for (int dy = 0; dy < dh; dy++) {

@@ -39,7 +39,7 @@ def test_scene_against_reference_outputs(oracle, key):
     # NMS + ordering + ids, pinned by the reference's heatmap_nms(bool_refine_center=False)
     jl0, _ = oracle.heatmap_nms(heat, 4, refine=False)
     assert np.array_equal(jl0, g["joint_list_norefine"])
-    # refined peaks: same oracle bicubic as when the fixture was made (regression guard; step itself unpinned)
+    # refined peaks: same oracle bicubic as when the fixture was made (regression guard; the step itself: test_cubic_reference_cpu.py)
     jl, _ = oracle.heatmap_nms(heat, 4, refine=True)
     assert np.array_equal(jl, g["joint_list"])
     assert np.array_equal(jl[:, 3:], jl0[:, 3:])
@@ -81,7 +81,8 @@ def test_flip_average_matches_numpy_semantics(oracle):
 
 
 def test_bicubic_restatement_properties(oracle):
-    """OpenCV is absent (parity unpinned): check the restatement's defining properties instead.
+    """The restatement's defining properties (its algorithm is pinned to an independent float64 reference and to torch by
+    test_cubic_reference_cpu.py; OpenCV is absent, so its own last bits stay unverified).
     Coefficients for the four x4 phases are exact dyadic rationals summing to 1; a constant image stays
     constant; upsampling commutes with transposition; phase table matches the closed form."""
     for x in (0.625, 0.875, 0.125, 0.375):
