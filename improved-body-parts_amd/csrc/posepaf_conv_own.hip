@@ -454,6 +454,10 @@ __global__ __launch_bounds__(NTHREADS) void k_conv_igemm(const ConvParams p) {
 // the tile geometry a template parameter (LGTW = log2 of the tile width: 7, 6, 5, 4 for image widths >= 128, 64, 32, 16).
 // Measured (tools/conv_ablate.py, 256 -> 256 @ 128 x 128, N = 128): 2.13 ms = 1.16 PFLOP/s; SQ_LDS_BANK_CONFLICT = 0.
 constexpr int TP = 512;  // output pixels per workgroup
+// Bits of k_conv3x3_halo's MASK template parameter.  The low bits (1 ... 1024) are the diagnostics build's ablation switches; this
+// one is a PRODUCT bit: the epilogue class "residual before the activation, with the channel sums" (pp_conv_own_res_sums_f16).
+constexpr int HALO_RES_SUMS = 2048;
+constexpr int HALO_DBG_BITS = HALO_RES_SUMS - 1;
 
 struct HaloParams {
     int TW, TH, lgTW;       // tile width (power of two, <= 128), height = 512 / TW
@@ -483,7 +487,8 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
     static_assert(D == 1 || PH < 0, "the collapsed upsample form has no dilation");
     // The tile geometry is a template parameter: every fragment address is then "lane register + immediate" (see R[][] below).
     constexpr int TW = 1 << LGTW, HWp = TW + 2 * D, TH = TP / TW;
-    constexpr int dbg = MASK;  // ablation switches are COMPILE-TIME (a runtime switch costs a branch per guarded instruction); 0 in production
+    constexpr int dbg = MASK & HALO_DBG_BITS;  // ablation switches are COMPILE-TIME (a runtime switch costs a branch per guarded instruction); 0 in
+                                               // production.  (MASK & HALO_RES_SUMS is no ablation: it selects the product's residual + sums epilogue.)
     constexpr int WN = BN / 64;          // 2
     constexpr int WM = 8 / WN;           // 4
     constexpr int PM = TP / WM;          // 128 pixels per wave
@@ -861,7 +866,16 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
             const int qy = q >> LGTW, qx = q & (TW - 1);
             return ((long)c_img * p.H + c_ty0 + qy) * p.W + c_tx0 + qx;
         });
-    else
+    else if constexpr ((MASK & HALO_RES_SUMS) != 0) {
+        // The residual-mode epilogue WITH the channel sums (pp_conv_own_res_sums_f16), an epilogue class of its own: y = act(conv +
+        // bias + extra) and the SE squeeze of y from the same registers.  PH < 0 and D == 1 (launcher).  Stacked images (a tile of
+        // gimg whole images, every pixel wave inside one of them): the image's WM / gimg waves are its splits, in order.
+        if (c_n0 + wn * 64 < p.K)
+            epilogue_body<1, PT, CT, true>(acc, p, lane, c_n0 + wn * 64, [&](int i) -> long {
+                const int q = wm * PM + i * 16 + (lane & 15);
+                return ((long)c_img * p.H + c_ty0 + (q >> LGTW)) * p.W + c_tx0 + (q & (TW - 1));
+            }, true, p.csum + ((((long)c_img * hp.tiles + c_tile) * WM) / hp.gimg + wm) * p.K);
+    } else
     epilogue_store<PT, CT>(acc, p, lane, c_n0 + wn * 64, [&](int i) -> long {
         const int q = wm * PM + i * 16 + (lane & 15);
         const int qy = q >> LGTW, qx = q & (TW - 1);
@@ -946,7 +960,7 @@ bool halo_geometry(const ConvParams &p, HaloParams &g) {
     } else {
         // a map lower than the tile (16 x 16: tile 16 wide x 32 rows): th / H whole images per tile, stacked, every wave's 128
         // pixels inside one of them
-        if (tw != p.W || th % p.H || p.H % (128 / tw) || p.N % (th / p.H) || p.csum) return false;
+        if (tw != p.W || th % p.H || p.H % (128 / tw) || p.N % (th / p.H) || (p.csum && p.mode != 1)) return false;   // (sums of stacked images: the residual form only)
         g.gimg = th / p.H;
         g.hrows = p.H + 2;
         g.tiles_x = 1;
@@ -1027,6 +1041,17 @@ int launch_halo_phase(const ConvParams &p, const HaloParams &g, hipStream_t st) 
     }
 }
 
+// the residual-mode epilogue with channel sums: instances of their own (MASK bit HALO_RES_SUMS), one per tile width
+int launch_halo_res_sums(const ConvParams &p, const HaloParams &g, hipStream_t st) {
+    switch (g.lgTW) {
+        case 7: return launch_halo_inst<HALO_RES_SUMS, 7>(p, g, st);
+        case 6: return launch_halo_inst<HALO_RES_SUMS, 6>(p, g, st);
+        case 5: return launch_halo_inst<HALO_RES_SUMS, 5>(p, g, st);
+        case 4: return launch_halo_inst<HALO_RES_SUMS, 4>(p, g, st);
+        default: return PP_ERR_UNSUPPORTED;
+    }
+}
+
 int launch_halo(const ConvParams &p, const HaloParams &g, hipStream_t st) {
     // POSEPAF_CONV_DBG (diagnostics): compile-time ablated instances; 0 = the product.  "No MFMA" exists only together with "no
     // fragment reads" (6, 7): a hand-placed ds_read whose result nothing consumes may land in a register the compiler has re-used.
@@ -1085,6 +1110,7 @@ struct PwParams {
     int kt1;               // a residual block's last 1x1 and its 1x1 skip convolution as ONE product (k-steps of 32 taken from x: kt1)
     _Float16 *pool;        // NULL, or the 2x2 max-pool of the produced tensor (m / 4 pixels x C_out): groups are then 2-row blocks
     int W;                 // pixels per image row (pool mode)
+    const _Float16 *pre_add = nullptr;   // PRE form: NULL, or a tensor of x's shape added to the scaled input (see k_pw)
 };
 
 // PT: 16-pixel tiles per wave and group (2: 32 pixels; 4: 64 pixels for the narrow inputs, whose groups are otherwise too small
@@ -1093,7 +1119,11 @@ struct PwParams {
 // output.  Compile-time, because a kernel that carries every form holds the registers of the richest one (the preloaded `extra` /
 // `extra2` vectors, the pooled rows): the plain stream then spilled at 64 and at 448 / 512 input channels.  (Forcing 128 registers -- two workgroups per
 // CU -- on the forms that need 130-136 was measured SLOWER, 0.39 against 0.33 ms for 256 -> 128 at 128 x 128 x 128.)
-template <int KT, int PT, int EX, bool POOL>
+// PRE: an INPUT class of its own (pp_pw_pre_f16), y = act(W (x * scale[n] + pre_add) + bias): the compress convolution of the
+// published variant (models/posenet_final.py: before_regress[s][0] reads SE(h)_s + cache_s).  The input fragment is multiplied and
+// then added to in binary16, each rounded -- the values a separate x * s pass and a separate tensor add would have written; neither
+// tensor exists in memory.
+template <int KT, int PT, int EX, bool POOL, bool PRE = false>
 __global__ __launch_bounds__(512) void k_pw(const PwParams p) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63;
@@ -1140,6 +1170,17 @@ __global__ __launch_bounds__(512) void k_pw(const PwParams p) {
                 const half8_t sv = *reinterpret_cast<const half8_t *>(sc + t * 32);
 #pragma unroll
                 for (int i = 0; i < PT; i++) xf[i][t] = xf[i][t] * sv;
+            }
+        }
+        if constexpr (PRE) {
+            if (p.pre_add) {
+#pragma unroll
+                for (int i = 0; i < PT; i++) {
+                    const long m = tile_m(i) + pl;
+                    const _Float16 *arow = p.pre_add + (m < p.M ? m : 0) * (KT * 32) + g * 8;
+#pragma unroll
+                    for (int t = 0; t < KT; t++) xf[i][t] = xf[i][t] + *reinterpret_cast<const half8_t *>(arow + t * 32);
+                }
             }
         }
         for (int c0 = 0; c0 < Nw; c0 += 64) {
@@ -1192,11 +1233,15 @@ __global__ __launch_bounds__(512) void k_pw(const PwParams p) {
 
 // pixels per group: 64 for the narrow inputs, 32 up to 512 channels, 16 beyond (all K of a group lives in registers: 32-pixel groups
 // of 640 / 704 channels would spill 70-100 registers)
-template <int KT, int PT, int EX, bool POOL>
+constexpr int kPwMaxLds = 144 * 1024;   // the most weight bytes pw_run lets one workgroup hold
+template <int KT, int PT, int EX, bool POOL, bool PRE = false>
 int launch_pw_form(const PwParams &p, int n_split, hipStream_t st) {
     const int lds = p.n_per_wg * KT * 64;   // n_per_wg rows x (KT * 32) halves
     static const int inst = g_inst_count.fetch_add(1);
-    if (const int rc = ensure_attr(reinterpret_cast<const void *>(&k_pw<KT, PT, EX, POOL>), lds, inst, st)) return rc;
+    // (the attribute is raised once per device: the PRE and the 768-channel instances ask for the largest size any caller of
+    // theirs can need, not for the first caller's)
+    if (const int rc = ensure_attr(reinterpret_cast<const void *>(&k_pw<KT, PT, EX, POOL, PRE>), (PRE || KT == 24) ? kPwMaxLds : lds, inst, st))
+        return rc;
     DevState *ds = dev_state();
     if (!ds) return PP_ERR_HIP;
     if (ds->ncu == 0) {
@@ -1208,7 +1253,7 @@ int launch_pw_form(const PwParams &p, int n_split, hipStream_t st) {
     // persistent grid: as many workgroups as are RESIDENT at once (registers and LDS decide: most forms hold one 8-wave workgroup
     // per CU, the leanest two) -- a workgroup beyond that would start when another ends and load the weights once more
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&k_pw<KT, PT, EX, POOL>), 512, (size_t)lds) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&k_pw<KT, PT, EX, POOL, PRE>), 512, (size_t)lds) !=
             hipSuccess || per_cu < 1)
         per_cu = 1;
     if (per_cu > 3) per_cu = 3;
@@ -1216,7 +1261,7 @@ int launch_pw_form(const PwParams &p, int n_split, hipStream_t st) {
     long gx = (long)ds->ncu * per_cu / n_split;
     if (gx < 1) gx = 1;
     if (gx * 8 > groups) gx = (groups + 7) / 8;
-    hipLaunchKernelGGL((k_pw<KT, PT, EX, POOL>), dim3((unsigned)gx, (unsigned)n_split), dim3(512), lds, st, p);
+    hipLaunchKernelGGL((k_pw<KT, PT, EX, POOL, PRE>), dim3((unsigned)gx, (unsigned)n_split), dim3(512), lds, st, p);
     return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
 }
 template <int KT, int PT = (KT <= 2 ? 4 : (KT <= 16 ? 2 : 1))>
@@ -1229,6 +1274,10 @@ int launch_pw_inst(const PwParams &p, int n_split, hipStream_t st) {
     }
     return ex == 0 ? launch_pw_form<KT, PT, 0, false>(p, n_split, st)
          : ex == 1 ? launch_pw_form<KT, PT, 1, false>(p, n_split, st) : launch_pw_form<KT, PT, 2, false>(p, n_split, st);
+}
+template <int KT, int PT = (KT <= 16 ? 2 : 1)>
+int launch_pw_pre(const PwParams &p, int n_split, hipStream_t st) {
+    return launch_pw_form<KT, PT, 0, false, true>(p, n_split, st);
 }
 
 // ------------------------------------------------------------------------------------------------ the stem: 7x7, stride 2
@@ -1348,13 +1397,24 @@ extern "C" {
 // y = act(conv1x1(x * scale[n]) + bias (+ extra)) [, y2 = y + extra2]: see k_pw.  x: DEVICE (m, c_in) fp16 (an NHWC activation,
 // m = n * h * w pixels); scale: DEVICE (m / hw, c_in) fp16 or NULL; w: DEVICE (c_out, c_in); bias fp16[c_out]; extra / extra2 /
 // y2: DEVICE (m, c_out) or NULL; y: DEVICE, pixel stride ldy >= c_out.  extra_mode as pp_conv_own_ex_f16 (0, 1, 2, 4).
-// c_in in {64, 128, 192, 256, 384, 448, 512, 640, 704}, c_out % 64 == 0, hw % 64 == 0 when scale is given; PP_ERR_UNSUPPORTED otherwise.
+// c_in in {64, 128, 192, 256, 384, 448, 512, 640, 704, 768}, c_out % 64 == 0, hw % 64 == 0 when scale is given; PP_ERR_UNSUPPORTED otherwise.
 PP_API int pp_pw_supported(int c_in, int c_out) {
-    return ((c_in == 64 || c_in == 128 || c_in == 192 || c_in == 256 || c_in == 384 || c_in == 448 || c_in == 512 || c_in == 640 || c_in == 704) && c_out % 64 == 0 && c_out >= 64) ? 1 : 0;
+    return ((c_in == 64 || c_in == 128 || c_in == 192 || c_in == 256 || c_in == 384 || c_in == 448 || c_in == 512 || c_in == 640 || c_in == 704 || c_in == 768) && c_out % 64 == 0 && c_out >= 64) ? 1 : 0;
 }
 static int pw_run(const void *x, const void *scale, const void *w, const void *bias, const void *extra, const void *extra2, void *y,
                   void *y2, long m, int hw, int c_in, int c_out, int ldy, int extra_mode, float slope, void *pool, int width, void *stream,
-                  const void *x2 = nullptr, int c_in2 = 0);
+                  const void *x2 = nullptr, int c_in2 = 0, bool pre_form = false, const void *pre_add = nullptr);
+
+// The input form y = act(conv1x1(x * scale[n] + pre_add) + bias): see k_pw (PRE).  scale: DEVICE (m / hw, c_in) fp16; pre_add:
+// DEVICE (m, c_in) fp16 or NULL; the product and then the sum are rounded to binary16, as the separate passes would round them.
+// c_in in {256, 384, 512, 640, 768}, c_out % 64 == 0, hw % 64 == 0, m % hw == 0; PP_ERR_UNSUPPORTED otherwise.
+PP_API int pp_pw_pre_f16(const void *x, const void *scale, const void *pre_add, const void *w, const void *bias, void *y, long m, int hw,
+                         int c_in, int c_out, int ldy, float slope, void *stream) {
+    if (!scale || (reinterpret_cast<uintptr_t>(pre_add) & 15)) return PP_ERR_BAD_ARG;
+    if (hw <= 0 || m % hw) return PP_ERR_UNSUPPORTED;
+    return pw_run(x, scale, w, bias, nullptr, nullptr, y, nullptr, m, hw, c_in, c_out, ldy, 0, slope, nullptr, 0, stream, nullptr, 0, true,
+                  pre_add);
+}
 
 PP_API int pp_pw_f16(const void *x, const void *scale, const void *w, const void *bias, const void *extra, const void *extra2, void *y,
                      void *y2, long m, int hw, int c_in, int c_out, int ldy, int extra_mode, float slope, void *stream) {
@@ -1384,7 +1444,7 @@ PP_API int pp_pw_cat_f16(const void *x, const void *x2, const void *w, const voi
 
 static int pw_run(const void *x, const void *scale, const void *w, const void *bias, const void *extra, const void *extra2, void *y,
                   void *y2, long m, int hw, int c_in, int c_out, int ldy, int extra_mode, float slope, void *pool, int width, void *stream,
-                  const void *x2, int c_in2) {
+                  const void *x2, int c_in2, bool pre_form, const void *pre_add) {
     // extra_mode 5 (this kernel only): the second output y2 = y + extra2 WITHOUT a tensor added before the activation
     if (!x || !w || !bias || !y || m <= 0 || hw <= 0 || ldy < c_out || extra_mode < 0 || extra_mode == 3 || extra_mode > 5 ||
         (extra_mode != 0 && extra_mode != 5) != (extra != nullptr) || (extra_mode >= 4) != (extra2 != nullptr) ||
@@ -1416,6 +1476,17 @@ static int pw_run(const void *x, const void *scale, const void *w, const void *b
     }
     p.n_per_wg = c_out / n_split;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (pre_form) {
+        p.pre_add = static_cast<const _Float16 *>(pre_add);
+        switch (c_in / 32) {   // the hourglass widths of the published variant: 256 + 128 s
+            case 8: return launch_pw_pre<8>(p, n_split, st);
+            case 12: return launch_pw_pre<12>(p, n_split, st);
+            case 16: return launch_pw_pre<16>(p, n_split, st);
+            case 20: return launch_pw_pre<20>(p, n_split, st);
+            case 24: return launch_pw_pre<24>(p, n_split, st);
+            default: return PP_ERR_UNSUPPORTED;
+        }
+    }
     switch (c_in / 32) {
         case 2: return launch_pw_inst<2>(p, n_split, st);
         case 4: return launch_pw_inst<4>(p, n_split, st);
@@ -1426,6 +1497,8 @@ static int pw_run(const void *x, const void *scale, const void *w, const void *b
         case 16: return launch_pw_inst<16>(p, n_split, st);
         case 20: return launch_pw_inst<20>(p, n_split, st);   // 256 + 384, 320 + ... : the second hourglass level's [t ; x]
         case 22: return launch_pw_inst<22>(p, n_split, st);
+        case 24:   // 768, the innermost hourglass width: the plain stream only (the forms that add tensors do not fit its registers cleanly)
+            return (p.e.mode == 0 && !p.pool) ? launch_pw_form<24, 1, 0, false>(p, n_split, st) : PP_ERR_UNSUPPORTED;
         default: return PP_ERR_UNSUPPORTED;
     }
 }
@@ -1591,6 +1664,36 @@ PP_API int pp_conv_own_sums_f16(const void *x, const void *w, const void *bias, 
     HaloParams g;
     if (!halo_geometry(p, g)) return PP_ERR_UNSUPPORTED;
     return launch_halo(p, g, st);
+}
+
+// The same with a residual: y = act(conv + bias + residual) -- the last block of a level of the published variant's hourglass
+// (models/layers_transposed_final.py: `up1 += deconv2`, then the LeakyReLU) -- and the partial sums of the binary16 values it stores,
+// laid out and consumed (pp_channel_mean_finish_f16 / pp_se_gains_f16) as pp_conv_own_sums_f16's.  residual: DEVICE (n, h, w,
+// c_out).  Also takes maps lower than a tile (16 x 16: whole images stacked in one tile, n a multiple of the images per tile):
+// pp_conv_own_res_sums_splits(h, wd) gives the splits per image (0: the shape is not taken).
+PP_API int pp_conv_own_res_sums_splits(int h, int wd) {
+    ConvParams q;
+    q.R = 3, q.pad = 1, q.dil = 1, q.C = 32, q.K = 128, q.H = h, q.W = wd, q.N = 32, q.csum = nullptr, q.up = 0, q.ldx = 0, q.mode = 1;
+    HaloParams g;
+    return halo_geometry(q, g) ? g.tiles * 4 / g.gimg : 0;
+}
+PP_API int pp_conv_own_res_sums_f16(const void *x, const void *w, const void *bias, const void *residual, void *y, void *sums_ws, int n,
+                                    int h, int wd, int c_in, int c_out, float slope, void *stream) {
+    if (!x || !w || !bias || !residual || !y || !sums_ws || n <= 0 || h <= 0 || wd <= 0) return PP_ERR_BAD_ARG;
+    if (!pp_conv_own_supported(c_in, c_out, 3) || !(slope >= 0.f && slope <= 1.f)) return PP_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(y) |
+         reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(sums_ws)) & 15)
+        return PP_ERR_BAD_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ConvParams p;
+    p.x = static_cast<const _Float16 *>(x), p.w = static_cast<const _Float16 *>(w), p.bias = static_cast<const _Float16 *>(bias);
+    p.extra = static_cast<const _Float16 *>(residual), p.extra2 = nullptr, p.up = 0, p.y = static_cast<_Float16 *>(y), p.y2 = nullptr, p.zero = nullptr;
+    p.N = n, p.H = h, p.W = wd, p.C = c_in, p.K = c_out, p.R = 3, p.pad = 1, p.dil = 1, p.Ho = h, p.Wo = wd;
+    p.ldy = c_out, p.csum = static_cast<float *>(sums_ws), p.M = (long)n * h * wd, p.mode = 1, p.slope = slope, p.dbg = 0, p.stagger = -1;
+    p.pad_y = p.pad_x = 1, p.up_out = 0, p.py = p.px = 0;
+    HaloParams g;
+    if (!halo_geometry(p, g)) return PP_ERR_UNSUPPORTED;
+    return launch_halo_res_sums(p, g, st);
 }
 
 // conv3x3 / pad 1 behind a x2 nearest-neighbour upsample (the hourglass' `hg[i][3](upsample(low))`, models/layers_transposed.py:

@@ -111,22 +111,23 @@ def main():
     ap.add_argument("--run_refactor", action="store_true")
     ap.add_argument("--run_cpp", action="store_true")
     ap.add_argument("--checkpoint_path", "-p", default=None)
+    ap.add_argument("--arch", choices=("posenet", "final", "auto"), default="posenet",
+                    help="network architecture: posenet = models/posenet.py (the development variant, default), final = models/posenet_final.py "
+                         "(the published 3- / 4-stage IMHN), auto = decided from the checkpoint's keys")
     ap.add_argument("--synthetic", type=int, default=0, help="no --image: a random 512x512 image with this many injected people")
     a = ap.parse_args()
     if a.run_cpp and not a.run_refactor:
         raise SystemExit("--run_cpp only exists on the refactored path (demo_image.py:118)")
     import torch
     from config.config import GetConfig, TrainingOpt
-    from models.posenet import NetworkEval
     from posepaf import skeleton as sk, synth
     from posepaf.fused_model import FusedIMHN
-    from posepaf.model_init import deterministic_init
+    from posepaf.model_init import build_network
     opt, config = TrainingOpt(), GetConfig(TrainingOpt.config_name)
-    net = NetworkEval(opt, config, bn=True).eval()
-    if a.checkpoint_path:
-        net.load_state_dict(torch.load(a.checkpoint_path, map_location="cpu", weights_only=True)["weights"])   # demo_image.py:292-293
-    else:
-        deterministic_init(net, 7)
+    try:
+        net, _ = build_network(a.arch, a.checkpoint_path, 7)   # demo_image.py:292-293 (strict)
+    except ValueError as e:
+        raise SystemExit(str(e))
     model = FusedIMHN.from_network(net).eval().cuda().half().to(memory_format=torch.channels_last)
     inject = None
     if a.image:

@@ -60,6 +60,9 @@ def parse(argv=None):
     ap.add_argument("--run_refactor", action="store_true")
     ap.add_argument("--run_cpp", action="store_true")
     ap.add_argument("--checkpoint_path", "-p", default=None, help="reference checkpoint (.pth with a 'weights' entry)")
+    ap.add_argument("--arch", choices=("posenet", "final", "auto"), default="posenet",
+                    help="network architecture: posenet = models/posenet.py (the development variant, default), final = models/posenet_final.py "
+                         "(the published 3- / 4-stage IMHN), auto = decided from the checkpoint's keys")
     ap.add_argument("--ann_file", default=None, help="COCO keypoint annotation JSON (evaluate.py:237-246)")
     ap.add_argument("--img_dir", default=None, help="directory of the annotation's images (evaluate.py:263)")
     ap.add_argument("--all_images", action="store_true", help="with --ann_file: every image, not only those with a person "
@@ -569,18 +572,15 @@ def main(argv=None):
     torch.backends.cudnn.benchmark = True
 
     from config.config import GetConfig, TrainingOpt
-    from models.posenet import NetworkEval
     from posepaf.api import PosePostProcessor, records_to_numpy
     from posepaf.fused_model import FusedIMHN
-    from posepaf.model_init import deterministic_init
+    from posepaf.model_init import build_network
 
     opt, config = TrainingOpt(), GetConfig(TrainingOpt.config_name)
-    net = NetworkEval(opt, config, bn=True).eval()
-    if a.checkpoint_path:
-        ckpt = torch.load(a.checkpoint_path, map_location="cpu", weights_only=True)
-        net.load_state_dict(ckpt["weights"])       # evaluate.py:308-309 (strict)
-    else:
-        deterministic_init(net, 7)
+    try:
+        net, _ = build_network(a.arch, a.checkpoint_path, 7)       # evaluate.py:308-309 (strict)
+    except ValueError as e:
+        raise SystemExit(str(e))
     model = FusedIMHN.from_network(net).eval().to(dev).half().to(memory_format=torch.channels_last)
 
     # ---- data

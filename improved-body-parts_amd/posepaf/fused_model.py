@@ -13,7 +13,9 @@ Only the 7x7 stride-2 stem and the 50-channel heads stay on PyTorch-ROCm (MIOpen
   * LeakyReLU applied in place on the conv output
 
 `FusedIMHN.from_network(NetworkEval)` takes the weights of the checkpoint-compatible definition in
-models/posenet.py, so a reference checkpoint loads there (strict=True) and is then folded here.
+models/posenet.py, so a reference checkpoint loads there (strict=True) and is then folded here.  A NetworkEval of
+models/posenet_final.py (the published 3- / 4-stage variant: plain 3x3 hourglass blocks, SE on the hourglass outputs, a 1x1
+compress convolution in front of before_regress) comes back as a FusedIMHNFinal, built from the same pieces.
 """
 from __future__ import annotations
 
@@ -47,6 +49,11 @@ USE_FOLDED_MERGE = True     # merge_preds(head(f)) is linear in f: folded into m
 USE_CAT_SKIP = True         # a residual block's last 1x1 and its 1x1 skip convolution as one product over [t ; x]
 USE_SE_KERNEL = True        # the SE block's excitation (two tiny linear layers, LeakyReLU, sigmoid) in one launch per block
 USE_POOL_FUSION = True      # the hourglass' 2x2 max-pools leave the 1x1 kernel that produces their input as a second output
+# (the published variant, models/posenet_final.py)
+USE_RES_SUM_FUSION = True   # the SE squeeze of an hourglass output leaves the residual-mode 3x3 kernel that produces it
+USE_PRE_FUSION = True       # the compress convolution reads x * s + cache: neither SE(h) nor SE(h) + cache is written
+PW_TUNE_MAX_CIN = 704       # widest input the PLAIN 1x1 convolution's candidate list offers pp_pw_f16 (the 768-channel instance
+                            # came with the published variant; the list a models/posenet.py network is tuned over stays as it was)
 _conv_choice: dict = {}   # shape key -> tile configuration id, or -1 = MIOpen convolution + k_bias_act pass
 _conv_timing: dict = {}   # shape key -> {"miopen": ms, cfg: ms, ...} measured by the autotune (diagnostics)
 _conv_calls: dict = {}    # shape key -> number of forward() calls since import (diagnostics)
@@ -465,7 +472,8 @@ class FConv(nn.Module):
         best, best_t, times = -1, float("inf"), {}
         own = [c_ for c_ in OWN_VARIANTS if USE_OWN_CONV and L.pp_conv_own_supported(x.shape[1], self.weight.shape[0],
                                                                                      self.weight.shape[2])]
-        if USE_PW and USE_OWN_CONV and self.weight.shape[2] == 1 and L.pp_pw_supported(x.shape[1], self.weight.shape[0]):
+        if (USE_PW and USE_OWN_CONV and self.weight.shape[2] == 1 and x.shape[1] <= PW_TUNE_MAX_CIN
+                and L.pp_pw_supported(x.shape[1], self.weight.shape[0])):
             own = own + [PW_VARIANT]
         for cfg in list(range(L.pp_conv_num_configs())) + own:
             if self._fused_launch(cfg, x, extra, mode, y) != 0:
@@ -516,14 +524,14 @@ class FConv(nn.Module):
         from . import _lib
         n, c, h, w = low.shape
         k = self.weight.shape[0]
-        mode = 3 if post2 is not None else 2
+        mode = 3 if post2 is not None else (2 if post is not None else 0)
 
         def run(choice):
             bn = UP2_COLLAPSED_BN[choice - 2] if choice >= 2 else 0
             if bn and (not USE_COLLAPSED_UP2 or k % (bn if bn != 512 else 64)):
                 return None
             x, y = _cl(low), self._out(low, 2 * h, 2 * w)
-            e1, e2 = _cl(post), (_cl(post2) if post2 is not None else None)
+            e1, e2 = (_cl(post) if post is not None else None), (_cl(post2) if post2 is not None else None)
             if bn:
                 rc = _lib.load().pp_conv_up2_collapsed_f16(_ptr(x), _ptr(self._collapsed_weights()), _ptr(self.bias), _ptr(e1), _ptr(e2),
                                                            _ptr(y), n, h, w, c, k, mode, self._slope, bn, _stream(x))
@@ -534,12 +542,15 @@ class FConv(nn.Module):
         return run
 
     def forward_up2(self, low, post, post2=None):
-        """act(conv(upsample2(low)) + bias) + post (+ post2), three ways, the fastest kept per shape (timed once):
+        """act(conv(upsample2(low)) + bias) (+ post (+ post2)), three ways, the fastest kept per shape (timed once):
         0 separate: upsample2 -> convolution (-> add3);  1 the upsample read through the 3x3 halo kernel's own loads, adds in its
         epilogue (pp_conv_own_ex_f16);  2.. the COLLAPSED form (pp_conv_up2_collapsed_f16): four 2x2 convolutions of the
         half-resolution tensor, 2.25x fewer multiply-adds for the same real-number result (choice = 2 + the tile width index)."""
         n, c, h, w = low.shape
         key = ("up2", n, c, h, w, self.weight.shape[0], post2 is not None, bool(self.act))
+        if post is None:   # (models/layers_transposed_final.py: hg[i][3] has nothing added behind it)
+            assert post2 is None
+            key = key + ("nopost",)
 
         def separate():
             if post2 is None:
@@ -674,6 +685,86 @@ class FConv(nn.Module):
         run = self._mean_fused(x)
         out = run(partial) if _choose(key, run is not None, [(0, "separate", separate), (1, "fused", run)]) else None
         return separate() if out is None else out
+
+    def _res_mean_fused(self, x, res):
+        """forward_res_mean's one-launch form, where it applies: run(hand_over) as _mean_fused's"""
+        n, c, h, w = x.shape
+        k = self.weight.shape[0]
+        if not (USE_OWN_CONV and USE_SUM_FUSION and USE_RES_SUM_FUSION and x.is_cuda and x.dtype == torch.float16
+                and self.stride == (1, 1) and tuple(self.weight.shape[2:]) == (3, 3) and self.padding == (1, 1)
+                and self.dilation == (1, 1) and c % 32 == 0 and k % 64 == 0 and tuple(res.shape) == (n, k, h, w)):
+            return None
+        from . import _lib
+        L = _lib.load()
+        splits = L.pp_conv_own_res_sums_splits(h, w)
+        if splits <= 0:
+            return None
+
+        def run(hand_over=False):
+            xx, rr, y = _cl(x), _cl(res), self._out(x, h, w)
+            ws = torch.empty((n, splits, k), dtype=torch.float32, device=x.device)
+            rc = L.pp_conv_own_res_sums_f16(_ptr(xx), _ptr(self._w()), _ptr(self.bias), _ptr(rr), _ptr(y), _ptr(ws), n, h, w, c, k,
+                                            self._slope, _stream(x))
+            if rc != 0:
+                return None
+            if hand_over:
+                return y, (ws, splits, h * w)
+            mean = torch.empty((n, k), dtype=x.dtype, device=x.device)
+            _lib.check(L.pp_channel_mean_finish_f16(_ptr(ws), _ptr(mean), n, h * w, k, splits, _stream(x)))
+            return y, mean
+        return run
+
+    def forward_res_mean(self, x, res, partial: bool = False):
+        """-> (y, channel mean of y) with y = act(conv(x) + bias + res): forward_mean for the residual-mode epilogue
+        (pp_conv_own_res_sums_f16) -- the output of an hourglass level of models/layers_transposed_final.py (`up1 += deconv2`, then the
+        LeakyReLU), which the stage's SE block squeezes (models/posenet_final.py: channel_attention).  Timed once per shape against
+        convolution + the two-pass channel mean; partial as forward_mean's."""
+        n, c, h, w = x.shape
+        key = ("rmean", n, c, h, w, self.weight.shape[0], bool(self.act))
+
+        def separate():
+            y = self(x, res)
+            return y, channel_mean(y)
+
+        run = self._res_mean_fused(x, res)
+        out = run(partial) if _choose(key, run is not None, [(0, "separate", separate), (1, "fused", run)]) else None
+        return separate() if out is None else out
+
+    def _pre_fused(self, x, scale, pre_add):
+        """forward_pre's one-launch form, where it applies: run() -> y, or None when the kernel refuses the shape"""
+        n, c, h, w = x.shape
+        k = self.weight.shape[0]
+        if not (USE_PW and USE_OWN_CONV and USE_PRE_FUSION and x.is_cuda and x.dtype == torch.float16 and scale.dtype == torch.float16
+                and tuple(self.weight.shape[2:]) == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0) and (h * w) % 64 == 0
+                and (pre_add is None or pre_add.shape == x.shape)):
+            return None
+        from . import _lib
+        L = _lib.load()
+        if not L.pp_pw_supported(c, k):
+            return None
+
+        def run():
+            xx, sc, y = _cl(x), scale.contiguous(), self._out(x, h, w)
+            aa = _cl(pre_add) if pre_add is not None else None
+            rc = L.pp_pw_pre_f16(_ptr(xx), _ptr(sc), _ptr(aa), _ptr(self._w()), _ptr(self.bias), _ptr(y), n * h * w, h * w, c, k, k,
+                                 self._slope, _stream(x))
+            return y if rc == 0 else None
+        return run
+
+    def forward_pre(self, x, scale, pre_add=None):
+        """act(conv1x1(x * scale[n] + pre_add) + bias): the compress convolution of models/posenet_final.py (before_regress[s][0] reads
+        SE(h)_s + cache_s).  One launch of the streaming 1x1 kernel's input form (pp_pw_pre_f16: product and sum rounded to binary16
+        in registers, neither tensor written), timed once per shape against channel_scale -> tensor add -> convolution."""
+        n, c, h, w = x.shape
+        key = ("pre", n, c, h, w, self.weight.shape[0], pre_add is not None, bool(self.act))
+
+        def separate():
+            xs = channel_scale(x, scale)
+            return self(xs if pre_add is None else xs + pre_add)
+
+        run = self._pre_fused(x, scale, pre_add)
+        y = run() if _choose(key, run is not None, [(0, "separate", separate), (1, "fused", run)]) else None
+        return separate() if y is None else y
 
     def _pool_fused(self, x, res):
         """forward_pool's one-launch form, where it applies: run() -> (y, pooled), or None when the kernel refuses the shape"""
@@ -990,6 +1081,10 @@ class FusedIMHN(nn.Module):
         self.dil = nn.ModuleList([_fconv_from_block(d) for d in pre.dilation])
         self.hg = nn.ModuleList([FHourglass(h) for h in p.hourglass])
         self.feat = nn.ModuleList([nn.ModuleList([FFeature(s) for s in f.before_regress]) for f in p.features])
+        self._init_heads_and_merges(p)
+
+    def _init_heads_and_merges(self, p):
+        """outs / merge_features / merge_preds: the same modules in both architectures (models/posenet.py, models/posenet_final.py)"""
         self.head = nn.ModuleList([nn.ModuleList([FHead(c.conv, c.bn, c.relu is not None) for c in o]) for o in p.outs])
         self.mfeat = nn.ModuleList([nn.ModuleList([_fconv_from_block(m.conv) for m in ms]) for ms in p.merge_features])
         self.mpred = nn.ModuleList([nn.ModuleList([_fconv_from_block(m.conv) for m in ms]) for ms in p.merge_preds])
@@ -1017,6 +1112,11 @@ class FusedIMHN(nn.Module):
 
     @classmethod
     def from_network(cls, net):
+        """the fused form of a NetworkEval: FusedIMHN for models/posenet.py, FusedIMHNFinal for models/posenet_final.py"""
+        if cls is FusedIMHN:
+            from models import posenet_final
+            if isinstance(net.posenet, posenet_final.PoseNet):
+                return FusedIMHNFinal(net)
         return cls(net)
 
     def forward(self, imgs, stage_preds: bool = False):
@@ -1075,6 +1175,101 @@ class FusedIMHN(nn.Module):
         return q.conv_only(pred)
 
 
+class FHourglassFinal(nn.Module):
+    """The hourglass of the published variant (models/layers_transposed_final.py Hourglass): every block one 3x3 convolution.  Per level
+    [0] the skip path (no activation), [1] / [2] down / up, [3] behind the x2 nearest upsample (the collapsed / up2 forms), [4] with the
+    level's residual add BEFORE the activation: out = leaky(conv4(.) + b + up1) -- the residual-mode epilogue; the LeakyReLU module
+    [5] of the reference is that epilogue's activation.  The innermost level adds [6] (held at index 5 here)."""
+
+    def __init__(self, hg):
+        super().__init__()
+        self.depth = hg.depth
+        self.levels = nn.ModuleList()
+        for i in range(hg.depth):
+            mods = [_fconv_from_block(hg.hg[i][k]) for k in range(5)]
+            mods[4].act = True
+            if i == hg.depth - 1:
+                mods.append(_fconv_from_block(hg.hg[i][6]))
+            self.levels.append(nn.ModuleList(mods))
+
+    def _level(self, i, x, out, squeeze, pooled=None):
+        """pooled: maxpool2(x) when the producer of x already made it, else None; out[s] = (scale-s output, its channel mean -- or
+        the partial sums behind it -- when s is in `squeeze`, else None)"""
+        lv = self.levels[i]
+        up1 = lv[0](x)
+        low = lv[1](maxpool2(x) if pooled is None else pooled)
+        if i == self.depth - 1:
+            out[i + 1] = lv[5].forward_mean(low, partial=True) if i + 1 in squeeze else (lv[5](low), None)
+            low = out[i + 1][0]
+        else:
+            low = self._level(i + 1, low, out, squeeze)
+        d1 = lv[3].forward_up2(lv[2](low), None)
+        out[i] = lv[4].forward_res_mean(d1, up1, partial=True) if i in squeeze else (lv[4](d1, up1), None)
+        return out[i][0]
+
+    def forward(self, x, pooled=None, squeeze=range(5)):
+        """-> [(output of scale s, its squeeze or None) for the five scales]"""
+        out = {}
+        self._level(0, x, out, set(squeeze), pooled)
+        return [out[s] for s in range(self.depth + 1)]
+
+
+class FFeatureFinal(nn.Module):
+    """before_regress[s] of models/posenet_final.py: 1x1 compress (256 + 128 s -> 256) -> 3x3 -> 3x3, no SE at its end.  The compress
+    convolution applies the SE gains of the hourglass output and adds the stage cache while it reads."""
+
+    def __init__(self, seq):
+        super().__init__()
+        self.c1, self.c2, self.c3 = _fconv_from_block(seq[0]), _fconv_from_block(seq[1]), _fconv_from_block(seq[2])
+
+    def forward(self, h, gains, cache=None):
+        return self.c3(self.c2(self.c1.forward_pre(h, gains, cache)))
+
+
+class FusedIMHNFinal(FusedIMHN):
+    """The published 3- / 4-stage IMHN (models/posenet_final.py) in the fused form: forward(NHWC image batch in [0,1]) ->
+    (N, 50, H/4, W/4), the `[-1][0]` output of its NetworkEval.  Heads, merges and the folded merge are FusedIMHN's (the reference's
+    two files agree on them); backbone, hourglass, SE placement and before_regress are this variant's."""
+
+    def __init__(self, net):
+        nn.Module.__init__(self)
+        p = net.posenet
+        self.S, self.K = p.nstack, 5
+        pre = p.pre
+        self.stem = FStem(pre.conv1, pre.bn1, True)
+        self.res1, self.res2, self.res3 = FResidual(pre.res1), FResidual(pre.res2), FResidual(pre.res3)
+        self.hg = nn.ModuleList([FHourglassFinal(h) for h in p.hourglass])
+        self.att = nn.ModuleList([nn.ModuleList([FSE(se) for se in ses]) for ses in p.channel_attention])
+        self.feat = nn.ModuleList([nn.ModuleList([FFeatureFinal(s) for s in f.before_regress]) for f in p.features])
+        self._init_heads_and_merges(p)
+
+    def forward(self, imgs, stage_preds: bool = False):
+        """stage_preds=True (tests): -> the scale-0 prediction of EVERY stage, i.e. the reference's out[t][0] for t = 0..S-1."""
+        seen = []
+        x = self.stem(imgs.permute(0, 3, 1, 2))  # NHWC storage viewed as NCHW == channels_last: no copy
+        x, x_pooled = self.res3.forward_pool(self.res2(self.res1.forward_pool(x)[1]))
+        caches = None
+        for t in range(self.S):
+            last = t == self.S - 1
+            scales = range(1) if last else range(self.K)  # the last stage's coarse heads feed nothing
+            hg = self.hg[t](x, x_pooled, scales)
+            # SE(h)_s (+ cache_s) is never written: the gains and the cache enter the compress convolution's input read
+            feats = [self.feat[t][s](hg[s][0], self.att[t][s].gains(hg[s][0], hg[s][1]), None if caches is None else caches[s])
+                     for s in scales]
+            if last or stage_preds or not self.folded_merge:
+                preds = [self.head[t][s](feats[s]) for s in (scales if not self.folded_merge else range(1))]
+                seen.append(preds[0])
+            if last:
+                return seen if stage_preds else preds[0]
+            if self.folded_merge:   # merge_preds(head(.)) lives inside merge_features' weights: no head, no prediction merge
+                c0, x, x_pooled = self.mfeat[t][0].forward_dual(feats[0], None, x, want_pool=True)
+                caches = [c0] + [self.mfeat[t][s](feats[s]) for s in scales if s > 0]
+                continue
+            mp = [self._merge_pred(t, s, preds[s]) for s in scales]
+            c0, x, x_pooled = self.mfeat[t][0].forward_dual(feats[0], mp[0], x, want_pool=True)
+            caches = [c0] + [self.mfeat[t][s](feats[s], mp[s]) for s in scales if s > 0]
+
+
 class GraphedForward:
     """Replays module(x) from a HIP graph for a fixed input shape (launch-bound coarse levels: ~900 kernels)."""
 
@@ -1097,12 +1292,15 @@ class GraphedForward:
         return self.static_out
 
 
-def build_inference_model(device, fused: bool = True, seed: int = 7, dtype=torch.float16):
-    """Random-init (deterministic, name-seeded) IMHN ready for inference on `device`."""
+def build_inference_model(device, fused: bool = True, seed: int = 7, dtype=torch.float16, arch: str = "posenet", nstack: int | None = None):
+    """Random-init (deterministic, name-seeded) IMHN ready for inference on `device`.  arch: "posenet" (models/posenet.py, the
+    development variant) or "final" (models/posenet_final.py, the published 3- / 4-stage one); nstack: None = the configuration's."""
     from config.config import GetConfig, TrainingOpt
-    from models.posenet import NetworkEval
-    from .model_init import deterministic_init
-    net = NetworkEval(TrainingOpt(), GetConfig("Canonical"), bn=True).eval()
+    from .model_init import deterministic_init, network_class
+    opt = TrainingOpt()
+    if nstack is not None:
+        opt.nstack = nstack
+    net = network_class(arch)(opt, GetConfig("Canonical"), bn=True).eval()
     deterministic_init(net, seed)
     if not fused:
         return net.to(device=device, dtype=dtype).to(memory_format=torch.channels_last)

@@ -188,6 +188,14 @@ PP_API int pp_channel_mean_f16(const void *x, void *partial_ws, void *out, int n
 PP_API int pp_conv_own_sums_splits(int h, int w);
 PP_API int pp_conv_own_sums_f16(const void *x, const void *w, const void *bias, void *y, void *sums_ws, int n, int h, int wd, int c_in,
                                 int c_out, float slope, void *stream);
+/* The same with a residual: y = act(conv + bias + residual), residual DEVICE (n, h, w, c_out), and the partial sums of the binary16
+ * values it stores, laid out and consumed as pp_conv_own_sums_f16's -- the last block of a level of the published variant's
+ * hourglass (models/layers_transposed_final.py: `up1 += deconv2`, then the LeakyReLU), whose output the stage's SE block squeezes.
+ * Also takes maps lower than a tile (16 x 16: whole images stacked in one tile; n must be a multiple of the images per tile).
+ * splits = pp_conv_own_res_sums_splits(h, w) (0: the shape is not taken). */
+PP_API int pp_conv_own_res_sums_splits(int h, int w);
+PP_API int pp_conv_own_res_sums_f16(const void *x, const void *w, const void *bias, const void *residual, void *y, void *sums_ws, int n,
+                                    int h, int wd, int c_in, int c_out, float slope, void *stream);
 PP_API int pp_channel_mean_finish_f16(const void *partial_ws, void *out, int n, long hw, int channels, int splits, void *stream);
 /* The SE block's excitation (models/layers_transposed.py:289-310) in one launch: gains (n, c) fp16 = sigmoid(W2 leaky(W1 mean + b1)
  * + b2), one workgroup per sample, roundings as the fp16 torch modules it replaces.  Input: partial_ws (n, splits, c) fp32 channel
@@ -286,11 +294,17 @@ PP_API int pp_conv_up2_collapsed_f16(const void *x, const void *w4, const void *
  * separate x * s pass would; w: DEVICE (c_out, c_in); bias fp16[c_out]; extra / extra2 / y2: DEVICE (m, c_out) or NULL;
  * y: DEVICE with ldy >= c_out elements between pixels (a channel slice of a wider tensor when larger); hw = h * w.
  * extra_mode 0 / 1 / 2 / 4 as pp_conv_own_ex_f16; 5 = the second output y2 = y + extra2 without a tensor added before the
- * activation (extra = NULL).  pp_pw_supported: c_in in {64, 128, 192, 256, 384, 448, 512, 640, 704} (the sums of a two-input call included), c_out % 64 == 0;
+ * activation (extra = NULL).  pp_pw_supported: c_in in {64, 128, 192, 256, 384, 448, 512, 640, 704, 768} (the sums of a two-input call included), c_out % 64 == 0;
  * with `scale`, hw % 64 == 0 (a group of pixels must not straddle two images). */
 PP_API int pp_pw_supported(int c_in, int c_out);
 PP_API int pp_pw_f16(const void *x, const void *scale, const void *w, const void *bias, const void *extra, const void *extra2, void *y,
                      void *y2, long m, int hw, int c_in, int c_out, int ldy, int extra_mode, float slope, void *stream);
+/* An INPUT form of the same stream: y = act(conv1x1(x * scale[n] + pre_add) + bias) -- the compress convolution of the published
+ * variant (models/posenet_final.py: before_regress[s][0] reads SE(h)_s + cache_s).  scale: DEVICE (m / hw, c_in) fp16; pre_add:
+ * DEVICE (m, c_in) fp16 or NULL.  The product is rounded to binary16, then the sum is rounded to binary16, where the fp16 modules
+ * round them; neither tensor is written to memory.  c_in in {256, 384, 512, 640, 768}, c_out % 64 == 0, hw % 64 == 0. */
+PP_API int pp_pw_pre_f16(const void *x, const void *scale, const void *pre_add, const void *w, const void *bias, void *y, long m, int hw,
+                         int c_in, int c_out, int ldy, float slope, void *stream);
 /* The same with the 2x2 / stride-2 max-pool of the tensor it produces (y; y2 in mode 4) as one more output -- the hourglass pools
  * exactly these tensors (`low = hg[i][1](pool(x))`, models/layers_transposed.py:262-266), so its pooling passes disappear.
  * pool_out: DEVICE (n, h / 2, w / 2, c_out); width = w: a multiple of 32 (64 when c_in = 64); h even. */
