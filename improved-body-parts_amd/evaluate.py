@@ -7,6 +7,8 @@
     python evaluate.py --synthetic 512 --batch 32 --scales 1.0 --test_cfg thre2=0.05 mid_num=40 remove_recon=1   # original
         path with the reference's test_cfg keys as run-time values (or --config_file PATH: the [param] section of an INI file)
     python evaluate.py --run_refactor --run_cpp --synthetic 256 --render_dir out/    # + every image with its skeletons drawn
+    python evaluate.py --run_refactor --run_cpp --synthetic 5000 --ap device         # rows + OKS matching on every rank's own GPU,
+        AP / AP50 / AP75 / AP(M) / AP(L) / AR ... (--ap host: the same twelve values from the host function, for comparison)
     python evaluate.py --synthetic 256 --batch 32 --scales 0.5 1.0 1.5 --sizes 512x480,480x512,500x475   # original path: sizes
         that pad alike at every scale share one ragged bucket (POSEPAF_ORIGINAL_BUCKETS=exact: group by exact size instead)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --synthetic 5000 ...
@@ -102,6 +104,12 @@ def parse(argv=None):
                          "refuses the option")
     ap.add_argument("--render_format", choices=("npy", "png"), default="npy",
                     help="file format of --render_dir: .npy always works, .png goes through PIL (as demo_image.save_image)")
+    ap.add_argument("--ap", choices=("host", "device"), default=None,
+                    help="report the keypoint AP with the area-range columns (AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl; "
+                         "oks_eval.evaluate_keypoints_ranges) and the seconds of the evaluation's steps.  device: every rank builds "
+                         "the result rows and matches them against its shard's ground truth on its own GPU (pp_coco_rows_f32, "
+                         "pp_oks_match), rank 0 accumulates; host: rank 0 does all of it in Python.  Without the option the report "
+                         "is evaluate_keypoints' (range `all` only), as before")
     a = ap.parse_args(argv)
     a.test_cfg_dict = None
     if a.test_cfg is not None or a.config_file is not None:
@@ -525,6 +533,117 @@ def run_original(a, src, mine, model, post, dev):
     return local.view(-1), time.perf_counter() - t0, info
 
 
+# ------------------------------------------------------------------------------------------------ --ap host / device
+def ground_truth_of(src, indices, original):
+    """Ground truth of the images `indices`, as the default report derives it: from the annotation file, or from the injected
+    synthetic scene."""
+    if src.gts:
+        return {src.image_ids[i]: src.gts[src.image_ids[i]] for i in indices if src.image_ids[i] in src.gts}
+    gts = {}
+    if src.has_scenes:
+        for i in indices:
+            slot = src.scene_slot(i)
+            joints = synth.make_scene_at_scales(src.n_people(slot), 20_000 + slot, [(8, 8, 1.0)], img=src.shape(i)[0])[1] \
+                if original else src.scene(slot, *padded_shape(*src.shape(i)))[1]
+            gts[src.image_ids[i]] = oks_eval.gt_from_synth_joints(joints)
+    return gts
+
+
+AP_BLOB = (("order", np.int32, 20), ("scores", np.float32, 20), ("match", np.int8, 600), ("n_det", np.int32, 1), ("n_gt", np.int32, 3),
+           ("counts", np.int32, 1))
+
+
+def ap_on_device(src, mine, local_recs, dev, world, backend, S, original):
+    """--ap device, every rank: rows + matching of its own records on its own device against its own shard's ground truth, then one
+    gather of the per-image outputs (776 bytes of order / scores / flags / counts + the image's result rows).
+    -> ({name: array in global image order}, seconds of the ground-truth derivation, seconds of packing + kernels + gather)"""
+    from posepaf.ap_device import DeviceKeypointEval
+    idx = [int(i) for i in mine]
+    t0 = time.perf_counter()
+    gts = ground_truth_of(src, idx, original)
+    torch.cuda.synchronize(dev)
+    t1 = time.perf_counter()
+    ev = DeviceKeypointEval(dev, [src.image_ids[i] for i in idx], gts)
+    out = ev.match(local_recs[: len(idx) * RECORD_BYTES])
+    width = torch.zeros(1, dtype=torch.int64, device=dev)
+    if len(idx):
+        width[0] = out["counts"].max()
+    if world > 1:
+        import torch.distributed as dist
+        width = width if backend == "nccl" else width.cpu()
+        dist.all_reduce(width, op=dist.ReduceOp.MAX)
+    width = int(width.item())              # rows per image that travel: the most people any image of the set has
+    parts = [out[name].reshape(len(idx), n).contiguous().view(torch.uint8) for name, _, n in AP_BLOB]
+    parts.append(out["rows"][:, :width].reshape(len(idx), width * 52).contiguous().view(torch.uint8))
+    blob = torch.cat(parts, dim=1)
+    if world > 1:
+        shard = torch.zeros((S, blob.shape[1]), dtype=torch.uint8, device=dev)
+        shard[: len(idx)] = blob
+        merged = pdist.gather_rows(shard if backend == "nccl" else shard.cpu(), len(idx))
+    else:
+        merged = blob.cpu().numpy()
+    res, at = {}, 0
+    for name, dtype, n in AP_BLOB:
+        nbytes = n * np.dtype(dtype).itemsize
+        res[name] = np.ascontiguousarray(merged[:, at:at + nbytes]).view(dtype).reshape(len(merged), n)
+        at += nbytes
+    res["rows"] = np.ascontiguousarray(merged[:, at:]).view(np.float32).reshape(len(merged), width, 52)
+    res["match"] = res["match"].reshape(len(merged), 3, 10, 20)
+    res["n_det"], res["counts"] = res["n_det"].reshape(-1), res["counts"].reshape(-1)
+    return res, t1 - t0, time.perf_counter() - t1
+
+
+def report_with_ap(a, src, merged, summary, gathered, original):
+    """rank 0, --ap host / device: results.json, the twelve values and the seconds of each step into `summary`"""
+    from posepaf.ap_device import stage_b_inputs
+    ids = src.image_ids
+    has_gt = bool(src.gts) or src.has_scenes
+    key = "keypoint_ap" if src.gts else "synthetic_oks"
+    os.makedirs(os.path.dirname(os.path.abspath(a.dump_name)), exist_ok=True)
+    if a.ap == "device":
+        res, t_gt, t_match = gathered
+        t0 = time.perf_counter()
+        if has_gt:
+            order = sorted(range(len(ids)), key=ids.__getitem__)
+            summary[key] = oks_eval.accumulate_ranges(*stage_b_inputs(res["scores"], res["match"], res["n_det"], res["n_gt"], order))
+        t1 = time.perf_counter()
+        results = []
+        rows = res["rows"].astype(np.float64)
+        for i, c in enumerate(res["counts"]):
+            kps, scores = rows[i, :c, :51].tolist(), rows[i, :c, 51].tolist()
+            results.extend({"image_id": ids[i], "category_id": 1, "keypoints": kp, "score": sc} for kp, sc in zip(kps, scores))
+        with open(a.dump_name, "w") as f:
+            json.dump(results, f)
+        t2 = time.perf_counter()
+        summary["ap"] = {"path": "device", "seconds_rows_and_match": t_match, "seconds_accumulate": t1 - t0, "seconds_json": t2 - t1,
+                         "seconds_ground_truth": t_gt}
+    else:
+        t0 = time.perf_counter()
+        results, dts = [], {}
+        for i, rec in enumerate(merged):
+            if int(rec["status"]) & 32:      # PP_ST_FLOAT_COORDS (original path): x / y are float32 bit patterns
+                rec = rec.copy()
+                fx, fy = rec["humans"]["x"].view(np.float32), rec["humans"]["y"].view(np.float32)
+                rec["humans"]["x"], rec["humans"]["y"] = np.rint(fx).astype(np.int32), np.rint(fy).astype(np.int32)
+            r = coco.coco_results(ids[i], coco.humans_from_record(rec))     # evaluate.py:182-209
+            results.extend(r)
+            dts[ids[i]] = [{"keypoints": x["keypoints"], "score": x["score"]} for x in r]
+        t1 = time.perf_counter()
+        gts = ground_truth_of(src, range(len(ids)), original)
+        t2 = time.perf_counter()
+        per_image = [oks_eval.match_image(gts.get(k, []), dts.get(k, [])) for k in sorted(set(gts) | set(dts))]
+        t3 = time.perf_counter()
+        if has_gt:
+            summary[key] = oks_eval.accumulate_ranges(*oks_eval.concat_matches(per_image))
+        t4 = time.perf_counter()
+        with open(a.dump_name, "w") as f:
+            json.dump(results, f)
+        t5 = time.perf_counter()
+        summary["ap"] = {"path": "host", "seconds_rows_and_match": (t1 - t0) + (t3 - t2), "seconds_accumulate": t4 - t3,
+                         "seconds_json": t5 - t4, "seconds_ground_truth": t2 - t1}
+    summary["people_found"] = len(results)
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse(argv)
@@ -628,7 +747,18 @@ def main(argv=None):
         merged = records_to_numpy(local_recs[:len(mine) * RECORD_BYTES])
         dt = dt_local
 
-    if rank == 0:
+    gathered = ap_on_device(src, mine, local_recs, dev, world, backend, S, original) if a.ap == "device" else None
+    if rank == 0 and a.ap is not None:
+        summary = {"images": int(n_images), "world": world, "images_per_sec": n_images / dt, "seconds": dt,
+                   "images_per_gpu_per_step": a.batch, "rules": "original" if original else ("cpp" if a.run_cpp else "python"),
+                   "people_found": 0,
+                   "status_or": int(np.bitwise_or.reduce(merged["status"])) if len(merged) else 0}
+        if summary["status_or"] & 128:
+            summary["recon_undefined_images"] = int(np.count_nonzero(merged["status"] & 128))
+        summary.update(info)
+        report_with_ap(a, src, merged, summary, gathered, original)
+        print(json.dumps(summary, default=str))
+    elif rank == 0:
         results, dts, gts = [], {}, dict(src.gts)
         for i, rec in enumerate(merged):
             if int(rec["status"]) & 32:      # PP_ST_FLOAT_COORDS (original path): x / y are float32 bit patterns

@@ -27,6 +27,10 @@ HUMAN_DTYPE = np.dtype([("peak_id", "<i4", (NUM_PART,)), ("x", "<i4", (NUM_PART,
 RECORD_DTYPE = np.dtype([("n_humans", "<i4"), ("n_peaks", "<i4"), ("status", "<u4"), ("n_connections", "<i4"),
                          ("humans", HUMAN_DTYPE, (MAX_HUMANS,))])
 RECORD_BYTES = RECORD_DTYPE.itemsize
+# pp_gt_ann and the sizes of the evaluation entries (include/posepaf.h)
+GT_ANN_DTYPE = np.dtype([("keypoints", "<f8", (17, 3)), ("area", "<f8"), ("bbox", "<f8", (4,)), ("iscrowd", "<i4"),
+                         ("num_keypoints", "<i4"), ("has_bbox", "<i4"), ("reserved", "<i4")])
+COCO_ROW, AP_MAX_DETS, AP_MAX_GT, AP_THRESHOLDS, AP_RANGES = 52, 20, 128, 10, 3
 
 EXPORTS = [
     "pp_create", "pp_destroy", "pp_last_hip_error", "pp_status_string", "pp_device_available", "pp_process_batch", "pp_process_batch_py",
@@ -37,6 +41,7 @@ EXPORTS = [
     "pp_resize_u8_cubic", "pp_resize_u8_cubic_ragged", "pp_original_accumulate_all_ragged", "pp_original_finish_ragged",
     "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
     "pp_set_map_residency", "pp_map_residency", "pp_map_workspace_bytes", "pp_time_map_prepass", "pp_draw_humans_u8",
+    "pp_coco_rows_f32", "pp_oks_match",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -110,6 +115,9 @@ def load():
     L.pp_preprocess_u8.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pp_preprocess_u8_ragged.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pp_draw_humans_u8.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.pp_coco_rows_f32.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.pp_oks_match.argtypes = [vp, vp, C.c_int, vp, vp, ip, C.c_int, vp, ip, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               vp, vp, vp, vp, vp, vp, vp]
     L.pp_flip_average.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_pwconv_supported.argtypes = [C.c_int, C.c_int]
     L.pp_pwconv_f16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int, vp]

@@ -40,3 +40,25 @@ def gather_records(local: torch.Tensor, n_local_valid: int, group=None) -> np.nd
         idx = np.arange(r, total, world)[: counts[r]]
         merged[idx] = recs[r, : counts[r]]
     return merged
+
+
+def gather_rows(local: torch.Tensor, n_local_valid: int, group=None) -> np.ndarray:
+    """gather_records for any fixed-size per-image payload: local is a uint8 tensor (S, K), S = padded shard size and K the same on
+    every rank.  Returns on every rank the (sum(valid), K) uint8 rows of all ranks re-interleaved into global image order."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    S, K = local.shape
+    out = torch.empty(world * S * K, dtype=torch.uint8, device=local.device)
+    dist.all_gather_into_tensor(out, local.contiguous().view(-1), group=group)
+    counts = torch.zeros(world, dtype=torch.int64, device=local.device)
+    counts[rank] = n_local_valid
+    dist.all_reduce(counts, group=group)
+    rows = out.cpu().numpy().reshape(world, S, K)
+    counts = counts.cpu().numpy()
+    total = int(counts.sum())
+    merged = np.empty((total, K), np.uint8)
+    for r in range(world):
+        idx = np.arange(r, total, world)[: counts[r]]
+        merged[idx] = rows[r, : counts[r]]
+    return merged

@@ -102,6 +102,123 @@ def evaluate_keypoints(gts: dict, dts: dict) -> dict:
             "AR": float(recalls.mean()), "n_gt": n_gt, "n_dt": int(len(scores))}
 
 
+# ---------------------------------------------------------------------------------------------- area ranges
+# The same procedure for COCOeval's area ranges all / medium / large (its `small` range is not used for keypoints).  This is
+# the written specification of the device path (csrc/posepaf_eval.hip, posepaf/ap_device.py).  Range `all` restates
+# evaluate_keypoints and must give its values exactly; parity against pycocotools stays UNPINNED (library absent).
+AREA_RANGES = np.array([[0.0, 1e10], [32.0 ** 2, 96.0 ** 2], [96.0 ** 2, 1e10]])   # all, medium, large; both ends inclusive
+AREA_NAMES = ("all", "medium", "large")
+MAX_GT = 128                      # ground truths per image the device kernel holds (the host function has no limit)
+
+
+def detection_area(kpts) -> float:
+    """Area of a keypoint result as the COCO API sets it when it loads results: the box of ALL 17 (x, y) entries, the
+    (0, 0) entries of missing parts included."""
+    k = np.asarray(kpts, float).reshape(17, 3)
+    return float((k[:, 0].max() - k[:, 0].min()) * (k[:, 1].max() - k[:, 1].min()))
+
+
+def oks_matrix(g: list, d: list) -> np.ndarray:
+    """compute_oks of every (detection, ground truth) pair, (len(d), len(g)), ground truths in annotation order."""
+    oks = np.zeros((len(d), len(g)))
+    for i, dd in enumerate(d):
+        for j, gg in enumerate(g):
+            oks[i, j] = compute_oks(np.asarray(dd["keypoints"], float).reshape(17, 3),
+                                    np.asarray(gg["keypoints"], float).reshape(17, 3), float(gg["area"]), gg.get("bbox"))
+    return oks
+
+
+def match_image(g: list, d: list) -> dict:
+    """Stage A, one image.  g: ground-truth annotations, d: detections (any number, any order).
+    -> {"order": indices into d of the 20 best by score (stable), "scores": their scores,
+        "match": int8 (3, 10, n) in {1 true positive, 0 false positive, -1 ignored}, "n_gt": counted ground truths per range,
+        "oks": (n, len(g)) in annotation order}"""
+    order = sorted(range(len(d)), key=lambda i: -d[i]["score"])[:MAX_DETS]
+    d = [d[i] for i in order]
+    T = len(OKS_THRESHOLDS)
+    oks_all = oks_matrix(g, d)
+    base_ignore = np.array([bool(x.get("iscrowd", 0)) or x.get("num_keypoints", 1) == 0 for x in g], bool)
+    g_area = np.array([float(x["area"]) for x in g], float)
+    d_area = np.array([detection_area(x["keypoints"]) for x in d], float)
+    match = np.zeros((len(AREA_RANGES), T, len(d)), np.int8)
+    n_gt = np.zeros(len(AREA_RANGES), np.int64)
+    for ri, (lo, hi) in enumerate(AREA_RANGES):
+        ignore = base_ignore | (g_area < lo) | (g_area > hi)
+        n_gt[ri] = int((~ignore).sum())
+        gorder = np.argsort(ignore, kind="mergesort")  # non-ignored GT first
+        ignore = ignore[gorder]
+        crowd = np.array([bool(g[j].get("iscrowd", 0)) for j in gorder], bool)
+        oks = oks_all[:, gorder]
+        d_out = (d_area < lo) | (d_area > hi)
+        for ti, thr in enumerate(OKS_THRESHOLDS):
+            gt_taken = np.zeros(len(g), bool)
+            for i in range(len(d)):
+                best, best_j = min(thr, 1 - 1e-10), -1
+                for j in range(len(g)):
+                    if gt_taken[j] and not crowd[j]:   # a crowd region may absorb any number of detections
+                        continue
+                    if best_j > -1 and not ignore[best_j] and ignore[j]:
+                        break
+                    if oks[i, j] < best:
+                        continue
+                    best, best_j = oks[i, j], j
+                if best_j >= 0:
+                    gt_taken[best_j] = True
+                    match[ri, ti, i] = -1 if ignore[best_j] else 1
+                else:
+                    match[ri, ti, i] = -1 if d_out[i] else 0   # unmatched and outside the range: neither TP nor FP
+    return {"order": np.asarray(order, np.int32), "scores": np.array([x["score"] for x in d], float), "match": match,
+            "n_gt": n_gt, "oks": oks_all}
+
+
+def accumulate_ranges(scores, match, n_gt) -> dict:
+    """Stage B.  scores: (N,) of all kept detections, images in ascending image-id order, each image's in its stage-A order;
+    match: (3, 10, N) stage-A flags in the same order; n_gt: (3,) counted ground truths.  Vectorised restatement of the
+    accumulation in evaluate_keypoints: stable sort by -score, cumulative sums, monotone precision envelope, 101 recall
+    points."""
+    scores = np.asarray(scores, float).reshape(-1)
+    match = np.asarray(match).reshape(len(AREA_RANGES), len(OKS_THRESHOLDS), -1)
+    n_gt = [int(v) for v in np.asarray(n_gt).reshape(-1)]
+    T, R = len(OKS_THRESHOLDS), len(RECALL_POINTS)
+    order = np.argsort(-scores, kind="mergesort")
+    precisions = np.zeros((len(AREA_RANGES), T, R))
+    recalls = np.zeros((len(AREA_RANGES), T))
+    for ri in range(len(AREA_RANGES)):
+        if n_gt[ri] == 0 or len(scores) == 0:
+            continue
+        m = match[ri][:, order]
+        tp = np.cumsum(m == 1, axis=1).astype(float)
+        fp = np.cumsum(m == 0, axis=1).astype(float)
+        rc = tp / n_gt[ri]
+        pr = tp / (tp + fp + np.spacing(1))
+        recalls[ri] = rc[:, -1]
+        pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]
+        for ti in range(T):
+            inds = np.searchsorted(rc[ti], RECALL_POINTS, side="left")
+            valid = inds < pr.shape[1]
+            precisions[ri, ti, valid] = pr[ti, inds[valid]]
+    nan = float("nan")
+    ap = [float(precisions[ri].mean()) if n_gt[ri] else nan for ri in range(len(AREA_RANGES))]
+    return {"AP": ap[0], "AP50": float(precisions[0, 0].mean()), "AP75": float(precisions[0, 5].mean()), "APm": ap[1], "APl": ap[2],
+            "AR": float(recalls[0].mean()), "AR50": float(recalls[0, 0]), "AR75": float(recalls[0, 5]),
+            "ARm": float(recalls[1].mean()), "ARl": float(recalls[2].mean()), "n_gt": n_gt[0], "n_dt": int(len(scores))}
+
+
+def evaluate_keypoints_ranges(gts: dict, dts: dict) -> dict:
+    """evaluate_keypoints for the area ranges all / medium / large: stage A per image (match_image), stage B once
+    (accumulate_ranges).  Same inputs; returns AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl, n_gt, n_dt."""
+    per_image = [match_image(gts.get(k, []), dts.get(k, [])) for k in sorted(set(gts) | set(dts))]
+    return accumulate_ranges(*concat_matches(per_image))
+
+
+def concat_matches(per_image: list):
+    """stage-A outputs of the images, in order -> the (scores, match, n_gt) stage B takes"""
+    if not per_image:
+        return np.zeros(0), np.zeros((len(AREA_RANGES), len(OKS_THRESHOLDS), 0), np.int8), np.zeros(len(AREA_RANGES), np.int64)
+    return (np.concatenate([p["scores"] for p in per_image]), np.concatenate([p["match"] for p in per_image], axis=2),
+            np.sum([p["n_gt"] for p in per_image], axis=0))
+
+
 def gt_from_synth_joints(joints: np.ndarray) -> list:
     """synth.random_people joints (P, 18, 3; CMU order, flag 1 = present) -> COCO-style GT annotations."""
     from . import skeleton as sk

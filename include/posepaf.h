@@ -357,6 +357,55 @@ PP_API int pp_preprocess_u8_ragged(const void *images_u8, const int *sizes_dev, 
 PP_API int pp_draw_humans_u8(const pp_record *records_dev, const void *src_u8, void *dst_u8, const int *sizes_dev, int batch, int hp,
                              int wp, void *stream);
 
+/* COCO keypoint evaluation, the per-image half (reference evaluate.py:182-209 append_result and :274-279 COCOeval, here
+ * posepaf/oks_eval.py evaluate_keypoints_ranges stage A), on the records where they already are.  Both entries are asynchronous,
+ * allocate nothing, use no atomics and store every output word plainly on every launch: capturable.
+ *
+ * pp_coco_rows_f32: per record the humans with at least one peak_id >= 0, in record order, one row of PP_COCO_ROW = 52 floats
+ *   each: 17 x (x, y, 1) in COCO keypoint order (posepaf/skeleton.py ORDER_COCO), zeros for absent parts, then pp_human.score --
+ *   what coco.humans_from_record + coco.coco_results produce.  n_humans is clamped to [0, PP_MAX_HUMANS]; a PP_ST_FLOAT_COORDS
+ *   record's coordinates are rounded half to even first (np.rint).  Coordinates are exact up to +-2^24 (float32).
+ *   records_dev: DEVICE pp_record[batch]; rows_dev: DEVICE float[batch][PP_MAX_HUMANS][52], rows past the count are zero;
+ *   counts_dev: DEVICE int[batch]. */
+#define PP_COCO_ROW 52
+#define PP_AP_MAX_DETS 20    /* COCOeval maxDets for keypoints */
+#define PP_AP_MAX_GT 128     /* ground truths of one image the matching kernel holds (20 x 128 float64 OKS values in LDS) */
+#define PP_AP_THRESHOLDS 10  /* OKS 0.50:0.05:0.95 */
+#define PP_AP_RANGES 3       /* area ranges all, medium, large */
+/* One ground-truth annotation as the evaluation reads it: keypoints (x, y, v) in COCO order, the annotation's area, its box
+ * [x, y, w, h] (has_bbox = 0: the annotation has none, a ground truth without labelled keypoints then has OKS 0), the crowd
+ * flag and num_keypoints (0 = ignored). */
+typedef struct {
+    double keypoints[17][3];
+    double area;
+    double bbox[4];
+    int32_t iscrowd;
+    int32_t num_keypoints;
+    int32_t has_bbox;
+    int32_t reserved;
+} pp_gt_ann;
+PP_API int pp_coco_rows_f32(const pp_record *records_dev, int batch, float *rows_dev, int *counts_dev, void *stream);
+/* pp_oks_match: one wave per image.  rows_dev / counts_dev: pp_coco_rows_f32's outputs (counts clamped to [0, PP_MAX_HUMANS]).
+ *   gt_dev: DEVICE pp_gt_ann[], the annotations of ground-truth slot s at [gt_offsets[s], gt_offsets[s + 1]); gt_offsets_dev /
+ *   gt_offsets_host: int[n_slots + 1], the SAME values on the device (read by the kernel) and on the host (argument checks);
+ *   slots_dev / slots_host: int[batch], the slot of image b, both NULL = image b uses slot b.  thresholds: HOST double[10],
+ *   area_ranges: HOST double[3][2] (lo, hi; both ends belong to the range) -- the caller's own values, passed to the kernel by
+ *   value and never recomputed.  Per image:
+ *     order_dev  int[batch][20]          rows of the 20 best detections by score, ties in row order; -1 past n_det
+ *     scores_dev float[batch][20]        their scores; 0 past n_det
+ *     match_dev  int8[batch][3][10][20]  1 true positive, 0 false positive, -1 ignored (matched an ignored ground truth, or
+ *                                        unmatched with the detection's own area outside the range); 0 past n_det
+ *     n_det_dev  int[batch]              min(count, 20)
+ *     n_gt_dev   int[batch][3]           ground truths that count in each range (not crowd, num_keypoints != 0, area in range)
+ *     oks_dev    double[batch][20][128]  optional (NULL: not written): the OKS matrix, detections in score order, ground truths
+ *                                        in annotation order, 0 outside [n_det][count]
+ *   The OKS follows compute_oks one IEEE float64 operation at a time; exp is the device library's and the sum runs in keypoint
+ *   order.  An image with more than PP_AP_MAX_GT ground truths: PP_ERR_TOO_LARGE before any launch, never truncated. */
+PP_API int pp_oks_match(const float *rows_dev, const int *counts_dev, int batch, const pp_gt_ann *gt_dev, const int *gt_offsets_dev,
+                        const int *gt_offsets_host, int n_slots, const int *slots_dev, const int *slots_host, const double *thresholds,
+                        const double *area_ranges, int *order_dev, float *scores_dev, signed char *match_dev, int *n_det_dev,
+                        int *n_gt_dev, double *oks_dev, void *stream);
+
 /* A2 standalone: the arrays predict_refactor returns (utils/parse_skeletons.py:82-103).  net_out_dev as for
  * pp_process_batch; heat_hwc_dev: DEVICE float[batch][h][w][20], paf_hwc_dev: DEVICE float[batch][h][w][30]. */
 PP_API int pp_flip_average(const void *net_out_dev, int dtype, int batch, int h, int w, int flip, float *heat_hwc_dev,
