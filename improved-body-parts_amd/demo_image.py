@@ -3,12 +3,16 @@
 
     python demo_image.py --image photo.npy|.png --output result.png --run_refactor --run_cpp [-p checkpoint.pth]
     python demo_image.py --synthetic 6 --output result.npy --run_refactor --run_cpp     # offline: injected pose scene
+    python demo_image.py --synthetic 6 --output result.npy --device_draw                # original path, drawn by the GPU
 
 Same flags as the reference (--image, --output, --run_refactor, --run_cpp): with --run_refactor the refactored path
 (predict_refactor + heatmap_nms, then pafprocess with --run_cpp or find_connections / find_humans without), otherwise
 the original path (predict + find_peaks + find_connections + find_humans) -- through the reference-named functions of
 utils.parse_skeletons, so every stage runs on the GPU.  Rendering is NumPy (utils/draw.py); OpenCV / matplotlib are not
-needed.  Images: .npy (BGR uint8) always, other formats through PIL when it is importable.  Offline there is no
+needed.  With --device_draw the people are packed into one pp_record and drawn by the kernels the batched paths use:
+pp_draw_humans_u8 on the refactored branch (the same pixels as NumPy), pp_draw_limbs_u8 on the original branch.  There a
+record holds float32 coordinates, so the GPU draws the candidates ROUNDED to float32 where NumPy draws the float64 ones: a
+joint within a float32 ulp of a whole pixel, or a limb within one of a whole degree, can come out a pixel apart.  Images: .npy (BGR uint8) always, other formats through PIL when it is importable.  Offline there is no
 checkpoint, so --synthetic P adds a synthetic P-people scene to the network output (as bench.py does) to have people to draw."""
 import argparse
 import os
@@ -54,7 +58,16 @@ def humans_from_python_rules(person_to_joint_assoc, joint_candidates):
     return humans
 
 
-def process(ori_img, model, test_cfg, model_cfg, config, run_refactor, run_cpp, inject=None):
+def draw_on_device(canvas, rec, limbs):
+    """one record drawn on `canvas` (BGR uint8, (h, w, 3)) by the GPU: pp_draw_limbs_u8 (limbs) or pp_draw_humans_u8"""
+    import torch
+    from posepaf.render import draw_limbs_records, draw_records
+    images = torch.from_numpy(np.ascontiguousarray(canvas[None])).cuda()
+    records = torch.from_numpy(np.ascontiguousarray(rec).reshape(1).view(np.uint8).copy()).cuda()
+    return (draw_limbs_records if limbs else draw_records)(images, records)[0].cpu().numpy()
+
+
+def process(ori_img, model, test_cfg, model_cfg, config, run_refactor, run_cpp, inject=None, device_draw=False):
     """-> (canvas, humans): the reference's process() (demo_image.py:80-243) with the image already loaded"""
     from posepaf import skeleton as sk
     from utils import draw, parse_skeletons as ps
@@ -90,7 +103,7 @@ def process(ori_img, model, test_cfg, model_cfg, config, run_refactor, run_cpp, 
             if human.body_parts:
                 human.score = hm["score"]
                 humans.append(human)
-        canvas = draw.draw_humans(canvas, humans)
+        canvas = draw_on_device(canvas, rec, limbs=False) if device_draw else draw.draw_humans(canvas, humans)
         return canvas, humans
     heatmaps, pafs = ps.predict(ori_img, model, test_cfg, model_cfg, "", flip_avg=True, config=config)
     if inject is not None:
@@ -100,7 +113,11 @@ def process(ori_img, model, test_cfg, model_cfg, config, run_refactor, run_cpp, 
     connected, special = ps.find_connections(all_peaks, pafs.astype(np.float32), image_h, test_cfg, pairs)
     persons, cand = ps.find_humans(connected, special, all_peaks, test_cfg, pairs)
     humans = humans_from_python_rules(persons, cand)
-    canvas = draw.draw_limbs_original(canvas, persons, cand, sk.LIMB_PAIRS, sk.DRAW_LIST)
+    if device_draw:
+        from posepaf.render import persons_to_record
+        canvas = draw_on_device(canvas, persons_to_record(persons, cand, float_coords=True), limbs=True)
+    else:
+        canvas = draw.draw_limbs_original(canvas, persons, cand, sk.LIMB_PAIRS, sk.DRAW_LIST)
     return canvas, humans
 
 
@@ -115,6 +132,9 @@ def main():
                     help="network architecture: posenet = models/posenet.py (the development variant, default), final = models/posenet_final.py "
                          "(the published 3- / 4-stage IMHN), auto = decided from the checkpoint's keys")
     ap.add_argument("--synthetic", type=int, default=0, help="no --image: a random 512x512 image with this many injected people")
+    ap.add_argument("--device_draw", action="store_true",
+                    help="draw on the GPU from one packed record: pp_draw_humans_u8 with --run_refactor, pp_draw_limbs_u8 without "
+                         "(there the record's float32 coordinates are drawn, where NumPy draws the float64 candidates)")
     a = ap.parse_args()
     if a.run_cpp and not a.run_refactor:
         raise SystemExit("--run_cpp only exists on the refactored path (demo_image.py:118)")
@@ -149,7 +169,8 @@ def main():
                 return t.permute(1, 2, 0).numpy()[:img.shape[0], :img.shape[1]].astype(np.float64)
             inject = (up(heat), up(paf))
     t0 = time.time()
-    canvas, humans = process(img, model, sk.default_test_cfg(), sk.default_model_cfg(), config, a.run_refactor, a.run_cpp, inject)
+    canvas, humans = process(img, model, sk.default_test_cfg(), sk.default_model_cfg(), config, a.run_refactor, a.run_cpp, inject,
+                            a.device_draw)
     print("processing time is %.5f, %d people" % (time.time() - t0, len(humans)))
     save_image(a.output, canvas)
 

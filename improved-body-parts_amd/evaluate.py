@@ -7,6 +7,8 @@
     python evaluate.py --synthetic 512 --batch 32 --scales 1.0 --test_cfg thre2=0.05 mid_num=40 remove_recon=1   # original
         path with the reference's test_cfg keys as run-time values (or --config_file PATH: the [param] section of an INI file)
     python evaluate.py --run_refactor --run_cpp --synthetic 256 --render_dir out/    # + every image with its skeletons drawn
+    python evaluate.py --synthetic 64 --batch 32 --scales 0.5 1.0 1.5 --render_limbs_dir out/   # original path: + every image with
+        its people in the demo's ellipse / alpha-blend style, drawn on the GPU from the device-side records
     python evaluate.py --run_refactor --run_cpp --synthetic 5000 --ap device         # rows + OKS matching on every rank's own GPU,
         AP / AP50 / AP75 / AP(M) / AP(L) / AR ... (--ap host: the same twelve values from the host function, for comparison)
     python evaluate.py --synthetic 256 --batch 32 --scales 0.5 1.0 1.5 --sizes 512x480,480x512,500x475   # original path: sizes
@@ -100,10 +102,16 @@ def parse(argv=None):
     ap.add_argument("--render_dir", default=None, metavar="DIR",
                     help="with --run_refactor: draw every image's skeletons on the GPU (pp_draw_humans_u8, the refactored branch "
                          "of demo_image.py:174-192, inside the batch's graph) and write each image's own (h, w) canvas to "
-                         "DIR/<index in the set>.npy (BGR uint8).  The original path's ellipse drawing stays in demo_image.py and "
-                         "refuses the option")
+                         "DIR/<index in the set>.npy (BGR uint8).  The original path refuses the option: its ellipse drawing is "
+                         "--render_limbs_dir")
+    ap.add_argument("--render_limbs_dir", default=None, metavar="DIR",
+                    help="without --run_refactor: draw every image's people on the GPU in the style of the demo's original branch "
+                         "(pp_draw_limbs_u8: demo_image.py:218-240, rotated ellipses and joint rings blended 0.4 / 0.6) from the "
+                         "batch's device-side records, and write each image's own (h, w) canvas to DIR/<index in the set>.npy "
+                         "(BGR uint8).  --run_refactor refuses the option: that path's style is --render_dir")
     ap.add_argument("--render_format", choices=("npy", "png"), default="npy",
-                    help="file format of --render_dir: .npy always works, .png goes through PIL (as demo_image.save_image)")
+                    help="file format of --render_dir / --render_limbs_dir: .npy always works, .png goes through PIL (as "
+                         "demo_image.save_image)")
     ap.add_argument("--ap", choices=("host", "device"), default=None,
                     help="report the keypoint AP with the area-range columns (AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl; "
                          "oks_eval.evaluate_keypoints_ranges) and the seconds of the evaluation's steps.  device: every rank builds "
@@ -373,7 +381,10 @@ def run_original(a, src, mine, model, post, dev):
     kernel and the entry's x4 maps are warped back inside the same launch (pp_original_accumulate_all_affine).
     Synthetic runs take their scenes from a device-resident bank per (size, scale, angle) (64 scenes), like the refactored
     path; a rotated entry's scenes are rendered at the rotated positions (synth.make_scene_at_scales).  The banks of a ragged
-    bucket's sizes have equal map shapes and are concatenated once per bucket."""
+    bucket's sizes have equal map shapes and are concatenated once per bucket.
+    With --render_limbs_dir every batch is drawn after its finish from the records where they are (pp_draw_limbs_u8, a ragged
+    bucket with its own size rows) onto a canvas of the group's own -- the staged images are overwritten two batches later --
+    and each image's corner is written out."""
     from concurrent.futures import ThreadPoolExecutor
     from posepaf.original_path import (OriginalPathProcessor, RaggedBucket, RaggedUnsupported, group_by_bucket_key,
                                        preprocess_ragged, resize_images_u8)
@@ -428,12 +439,19 @@ def run_original(a, src, mine, model, post, dev):
                 setup_ragged(key, members)
             else:
                 setup_exact(*shapes[members[0]])
+    n_rendered = 0
+    if a.render_limbs_dir:
+        from demo_image import save_image
+        from posepaf.render import draw_limbs_records, limb_angle_table_dev
+        os.makedirs(a.render_limbs_dir, exist_ok=True)
+        limb_angle_table_dev(dev)                   # the device's cos / sin table: built once, outside the timed loop
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     copy_stream = torch.cuda.Stream(device=dev)
 
     def run_group(members, ragged_key=None):
         """one group through the double-buffered loop.  ragged_key None: every image is (H, W), the equal-size kernels."""
+        nonlocal n_rendered
         if ragged_key is None:
             H, W = shapes[members[0]]
             proc = OriginalPathProcessor(post, H, W, B)
@@ -443,6 +461,7 @@ def run_original(a, src, mine, model, post, dev):
             size_index = banks[(ragged_key, "sizes")]
         pinned = [torch.zeros((B, H, W, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
         staged = [torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+        canvas = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) if a.render_limbs_dir else None
         events = [None, None]
         batches = [members[b0:b0 + B] for b0 in range(0, len(members), B)]
 
@@ -503,11 +522,19 @@ def run_original(a, src, mine, model, post, dev):
                             maps = torch.addcmul(banks[(ragged_key, float(sc))].index_select(0, slots), maps, scale)
                         proc.accumulate(maps, *rg.pads(i), n_div)
                 rec = proc.finish(B, thre1)
+                if canvas is not None:   # reads staged[k]: before `done`
+                    draw_limbs_records(dev_imgs, rec, rg.dev[0] if ragged_key is not None else None, out=canvas)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
             events[k][1] = done
             local.index_copy_(0, torch.tensor(loc, dtype=torch.int64, device=dev), rec.view(B, RECORD_BYTES)[:n])
             stage(j + 1)                            # the next batch is decoded and uploaded while this one computes
+            if canvas is not None:   # the canvas is the group's until the next batch's draw: bring it to the host now
+                canvases = canvas[:n].cpu().numpy()
+                for q, k_local in enumerate(loc):
+                    h, w = shapes[k_local]
+                    save_image(os.path.join(a.render_limbs_dir, "%06d.%s" % (int(mine[k_local]), a.render_format)), canvases[q, :h, :w])
+                    n_rendered += 1
 
     n_ragged = 0
     for key, members, ragged in groups:
@@ -530,6 +557,8 @@ def run_original(a, src, mine, model, post, dev):
     if a.rotation_search is not None:
         info["rotation_search"] = angles
     info["test_cfg"] = post.test_cfg      # the configuration in force, read back from the context
+    if a.render_limbs_dir:
+        info["rendered_files"] = n_rendered
     return local.view(-1), time.perf_counter() - t0, info
 
 
@@ -674,6 +703,9 @@ def main(argv=None):
     if a.render_dir is not None and original:
         raise SystemExit("--render_dir draws from the records of the refactored path only (add --run_refactor): the original "
                          "path's ellipse / alpha-blend drawing (demo_image.py:218-240) stays on NumPy in demo_image.py")
+    if a.render_limbs_dir is not None and not original:
+        raise SystemExit("--render_limbs_dir draws from the records of the original path only (drop --run_refactor): the "
+                         "refactored path draws its own style with --render_dir")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

@@ -41,6 +41,7 @@ EXPORTS = [
     "pp_resize_u8_cubic", "pp_resize_u8_cubic_ragged", "pp_original_accumulate_all_ragged", "pp_original_finish_ragged",
     "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
     "pp_set_map_residency", "pp_map_residency", "pp_map_workspace_bytes", "pp_time_map_prepass", "pp_draw_humans_u8",
+    "pp_draw_limbs_u8", "pp_limb_angle_table", "pp_limb_angle_deg",
     "pp_coco_rows_f32", "pp_oks_match",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
@@ -115,6 +116,9 @@ def load():
     L.pp_preprocess_u8.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pp_preprocess_u8_ragged.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pp_draw_humans_u8.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.pp_draw_limbs_u8.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.pp_limb_angle_table.argtypes = [C.POINTER(C.c_double)]
+    L.pp_limb_angle_deg.argtypes = [C.c_double, C.c_double]
     L.pp_coco_rows_f32.argtypes = [vp, C.c_int, vp, vp, vp]
     L.pp_oks_match.argtypes = [vp, vp, C.c_int, vp, vp, ip, C.c_int, vp, ip, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                vp, vp, vp, vp, vp, vp, vp]

@@ -347,7 +347,7 @@ PP_API int pp_preprocess_u8_ragged(const void *images_u8, const int *sizes_dev, 
  * radius 4.5 in CocoColors[part] (utils/common.py:281-283), then CocoPairsRender (:285-289) as lines of thickness 3 in
  * CocoColors[pair], later over earlier -- bit-equal to the NumPy renderer utils/draw.py:draw_humans(canvas, humans) (parity with
  * cv2's own rasteriser stays unpinned, as for draw.py).  The ellipse / alpha-blend style of the original branch
- * (demo_image.py:218-240) is not offered: its angle goes through atan2 / cos / sin.
+ * (demo_image.py:218-240) is pp_draw_limbs_u8 below.
  * records_dev: DEVICE pp_record[batch]; n_humans is clamped to [0, PP_MAX_HUMANS], peak_id[p] < 0 = part absent, and with
  * PP_ST_FLOAT_COORDS the joint is drawn at the truncated coordinate, as int(bp.x) does.  src_u8 / dst_u8: DEVICE (batch, hp, wp, 3)
  * BGR; dst_u8 == src_u8 draws in place, any other overlap is the caller's error.  sizes_dev: DEVICE int[2][batch] = heights, then
@@ -356,6 +356,26 @@ PP_API int pp_preprocess_u8_ragged(const void *images_u8, const int *sizes_dev, 
  * +-32767; beyond that nothing outside the image's pixels is written.  Asynchronous, nothing allocated: capturable. */
 PP_API int pp_draw_humans_u8(const pp_record *records_dev, const void *src_u8, void *dst_u8, const int *sizes_dev, int batch, int hp,
                              int wp, void *stream);
+
+/* The demo's other style (reference demo_image.py:218-240, the original branch; what `python demo_image.py` draws without
+ * flags): per limb type of DRAW_LIST (config/config.py:154) and per human a filled rotated ellipse between the two joints in
+ * LimbColors[board[t]] and black rings on the joints, each such drawing blended 0.4 / 0.6 into the canvas so far -- bit-equal to
+ * the NumPy renderer utils/draw.py:draw_limbs_original on the persons / candidates the record stands for
+ * (posepaf/render.py:record_to_persons).  Per pixel: the fold, in draw order (limb types outside, humans inside), of
+ * px = clip(rint(px * 0.4 + cur * 0.6), 0, 255) over the instances that hit it, cur = the ellipse colour where the ellipse hits
+ * and black where only a ring does; the geometry is spelled out in csrc/posepaf_limbs.hip.  The ellipse's angle
+ * k = int(degrees(atan2(dy, dx))) is found without a device libm (pp_limb_angle_deg), and cos / sin of k degrees come from
+ * angle_table_dev: a DEVICE copy of the 361 x 2 doubles pp_limb_angle_table fills on the HOST with the C library.
+ * Records, buffers, sizes_dev, the in-place form and the claim (coordinates within +-32767; a joint with a non-finite float32
+ * coordinate skips its limbs) are pp_draw_humans_u8's.  Asynchronous, nothing allocated: capturable. */
+PP_API int pp_draw_limbs_u8(const pp_record *records_dev, const void *src_u8, void *dst_u8, const int *sizes_dev, int batch, int hp,
+                            int wp, const double *angle_table_dev, void *stream);
+/* table_host[2 * (k + 180)] = cos, [2 * (k + 180) + 1] = sin of k * (pi / 180) for k = -180 .. 180, from the C library's cos / sin
+ * at run time: the bits of Python's math.cos(math.radians(k)) / math.sin(math.radians(k)).  Host work only. */
+PP_API int pp_limb_angle_table(double *table_host);
+/* int(math.degrees(math.atan2(dy, dx))) for finite dy, dx that are differences of int or float32 coordinates: the host instance
+ * of the function the kernel calls (no libm inside; exact directions by branches, a bisection on the table's signs elsewhere). */
+PP_API int pp_limb_angle_deg(double dy, double dx);
 
 /* COCO keypoint evaluation, the per-image half (reference evaluate.py:182-209 append_result and :274-279 COCOeval, here
  * posepaf/oks_eval.py evaluate_keypoints_ranges stage A), on the records where they already are.  Both entries are asynchronous,
