@@ -6,6 +6,15 @@
 
 #include "../../include/posepaf.h"
 
+// The skeleton's tables, ONE copy of the values for every translation unit that needs them on the device (each defines its own
+// __device__ array from the list: the library is built without relocatable device code).
+// limbs: utils/pafprocess/pafprocess.h:21-27 (== config/config.py:114-121); flip orders: config/config.py:150-152
+#define PP_LIMB_FROM_LIST {1, 1, 1, 1, 1, 0, 0, 14, 15, 1, 2, 3, 1, 5, 6, 1, 8, 9, 1, 11, 12, 0, 0, 2, 8, 5, 11, 16, 17, 8}
+#define PP_LIMB_TO_LIST {0, 14, 15, 16, 17, 14, 15, 16, 17, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 2, 5, 8, 12, 11, 9, 2, 5, 11}
+#define PP_FLIP_HEAT_ORD_LIST {0, 1, 5, 6, 7, 2, 3, 4, 11, 12, 13, 8, 9, 10, 15, 14, 17, 16, 18, 19}
+#define PP_FLIP_PAF_ORD_LIST \
+    {0, 2, 1, 4, 3, 6, 5, 8, 7, 12, 13, 14, 9, 10, 11, 18, 19, 20, 15, 16, 17, 22, 21, 25, 26, 23, 24, 28, 27, 29}
+
 namespace pp {
 
 // 160 KiB of LDS per CU (gfx950) minus room for the kernels' static __shared__ arrays (< 2 KB)

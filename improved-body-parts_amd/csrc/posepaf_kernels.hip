@@ -40,12 +40,21 @@ __device__ const int8_t d_limb_pairs[PP_NUM_LIMB][2] = {
     {1, 0},   {1, 14},  {1, 15},  {1, 16},  {1, 17},  {0, 14},  {0, 15},  {14, 16}, {15, 17}, {1, 2},
     {2, 3},   {3, 4},   {1, 5},   {5, 6},   {6, 7},   {1, 8},   {8, 9},   {9, 10},  {1, 11},  {11, 12},
     {12, 13}, {0, 2},   {0, 5},   {2, 8},   {8, 12},  {5, 11},  {11, 9},  {16, 2},  {17, 5},  {8, 11}};
-constexpr int kLimbA[PP_NUM_LIMB] = {1, 1, 1, 1, 1, 0, 0, 14, 15, 1, 2, 3, 1, 5, 6, 1, 8, 9, 1, 11, 12, 0, 0, 2, 8, 5, 11, 16, 17, 8};
-constexpr int kLimbB[PP_NUM_LIMB] = {0, 14, 15, 16, 17, 14, 15, 16, 17, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 2, 5, 8, 12, 11, 9, 2, 5, 11};
+constexpr int kLimbA[PP_NUM_LIMB] = PP_LIMB_FROM_LIST;   // the lists: posepaf_internal.h (shared with posepaf_synth.hip)
+constexpr int kLimbB[PP_NUM_LIMB] = PP_LIMB_TO_LIST;
+constexpr bool limb_pairs_match_lists() {
+    constexpr int pairs[PP_NUM_LIMB][2] = {
+        {1, 0},   {1, 14},  {1, 15},  {1, 16},  {1, 17},  {0, 14},  {0, 15},  {14, 16}, {15, 17}, {1, 2},
+        {2, 3},   {3, 4},   {1, 5},   {5, 6},   {6, 7},   {1, 8},   {8, 9},   {9, 10},  {1, 11},  {11, 12},
+        {12, 13}, {0, 2},   {0, 5},   {2, 8},   {8, 12},  {5, 11},  {11, 9},  {16, 2},  {17, 5},  {8, 11}};
+    for (int l = 0; l < PP_NUM_LIMB; l++)
+        if (pairs[l][0] != kLimbA[l] || pairs[l][1] != kLimbB[l]) return false;
+    return true;
+}
+static_assert(limb_pairs_match_lists(), "d_limb_pairs and PP_LIMB_FROM_LIST / PP_LIMB_TO_LIST disagree");
 // config/config.py:150-152
-__device__ const int8_t d_flip_heat_ord[PP_NUM_HEAT] = {0, 1, 5, 6, 7, 2, 3, 4, 11, 12, 13, 8, 9, 10, 15, 14, 17, 16, 18, 19};
-__device__ const int8_t d_flip_paf_ord[PP_NUM_LIMB] = {0,  2,  1,  4,  3,  6,  5,  8,  7,  12, 13, 14, 9,  10, 11,
-                                                       18, 19, 20, 15, 16, 17, 22, 21, 25, 26, 23, 24, 28, 27, 29};
+__device__ const int8_t d_flip_heat_ord[PP_NUM_HEAT] = PP_FLIP_HEAT_ORD_LIST;
+__device__ const int8_t d_flip_paf_ord[PP_NUM_LIMB] = PP_FLIP_PAF_ORD_LIST;
 
 // OpenCV interpolateCubic(A = -0.75) at the four fractional phases of an x4 upsample:
 // fx = (dx + 0.5)/4 - 0.5  ->  frac = .625, .875, .125, .375 for dx mod 4 = 0..3.  All sixteen values are exact

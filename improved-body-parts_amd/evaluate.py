@@ -13,6 +13,8 @@
         AP / AP50 / AP75 / AP(M) / AP(L) / AR ... (--ap host: the same twelve values from the host function, for comparison)
     python evaluate.py --synthetic 256 --batch 32 --scales 0.5 1.0 1.5 --sizes 512x480,480x512,500x475   # original path: sizes
         that pad alike at every scale share one ragged bucket (POSEPAF_ORIGINAL_BUCKETS=exact: group by exact size instead)
+    python evaluate.py --run_refactor --run_cpp --synthetic 5000 --scenes device     # 5000 distinct scenes, each rendered on the
+        GPU from its joint list inside the batch's graph (default --scenes bank: 64 host-rendered scenes, image i shows i mod 64)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --synthetic 5000 ...
 
 What is kept from the reference: the flags --run_refactor / --run_cpp (:53-54; --run_cpp selects the C++ pafprocess rules --
@@ -56,7 +58,8 @@ from posepaf._lib import RECORD_BYTES  # noqa: E402
 from posepaf.engine import padded_shape  # noqa: E402
 
 IMAGE_EXT = (".jpg", ".jpeg", ".png", ".bmp")
-SCENE_BANK = 64          # distinct synthetic scenes per bucket shape (image i shows scene i mod 64)
+SCENE_BANK = 64          # --scenes bank: distinct synthetic scenes per bucket shape (image i shows scene i mod 64)
+SCENE_SEED = 20_000      # --scenes device: key of the counter-based noise (the scene id is the image's index in the set)
 
 
 def parse(argv=None):
@@ -118,7 +121,18 @@ def parse(argv=None):
                          "the result rows and matches them against its shard's ground truth on its own GPU (pp_coco_rows_f32, "
                          "pp_oks_match), rank 0 accumulates; host: rank 0 does all of it in Python.  Without the option the report "
                          "is evaluate_keypoints' (range `all` only), as before")
+    ap.add_argument("--scenes", choices=("bank", "device"), default="bank",
+                    help="where the injected scenes (--synthetic, --inject_gt) come from.  bank: rendered on the host before the "
+                         "run and kept in HBM -- 64 per bucket shape for --synthetic (image i shows scene i mod 64), one per image "
+                         "for --inject_gt.  device (with --run_refactor): every image's own scene, rendered from its joint list "
+                         "inside the batch's graph (pp_render_scenes) -- --synthetic N shows N distinct scenes and --inject_gt "
+                         "needs neither the bank nor --limit")
+    ap.add_argument("--scene_noise", type=float, default=0.02,
+                    help="--synthetic: sigma of the noise added to the injected scenes (both --scenes modes; the device renderer "
+                         "draws it from a counter-based generator, so the two modes' noise values differ)")
     a = ap.parse_args(argv)
+    if a.scene_noise < 0:
+        ap.error("--scene_noise must be >= 0")
     a.test_cfg_dict = None
     if a.test_cfg is not None or a.config_file is not None:
         try:
@@ -193,27 +207,28 @@ class CocoSource:
             raise SystemExit(f"{self.files[i]}: decoded size {im.shape[:2]} != annotation {self._shapes[i]}")
         return im
 
+    scene_noise = 0.0        # the injected annotation scenes carry no noise, in either --scenes mode
+
+    def scene_joints(self, i, hp=None, wp=None):
+        """joints (P, 18, 3) of image i's injected scene: the annotation's own keypoints (COCO order -> the 18 CMU parts, neck =
+        shoulder midpoint as in the reference's data pipeline; posepaf.synth_device.coco_to_joints)"""
+        from posepaf.synth_device import coco_to_joints
+        return coco_to_joints(self.gts[self.image_ids[i]])
+
+    def max_people(self, indices):
+        return max([len(self.gts[self.image_ids[i]]) for i in indices] + [1])
+
+    def distinct_scenes(self, device):
+        return len(self.image_ids)
+
     def bank_for_bucket(self, hp, wp, indices):
-        """--inject_gt (no weights offline): one GT-style scene per image, rendered from the annotation's own keypoints
-        (COCO order -> the 18 CMU parts, neck = shoulder midpoint as in the reference's data pipeline)."""
-        from posepaf import skeleton as sk
+        """--inject_gt --scenes bank (no weights offline): one GT-style scene per image, rendered on the host from the
+        annotation's own keypoints and kept in HBM."""
         if len(indices) * 2 * 50 * (hp // 4) * (wp // 4) * 2 > 64 << 30:
-            raise SystemExit("--inject_gt keeps one scene per image in HBM: use --limit")
+            raise SystemExit("--inject_gt --scenes bank keeps one scene per image in HBM: use --limit, or --scenes device")
         scenes = []
         for i in indices:
-            people = []
-            for g in self.gts[self.image_ids[i]]:
-                kp = np.asarray(g["keypoints"], np.float64).reshape(17, 3)
-                j = np.zeros((sk.NUM_PART, 3))
-                j[:, 2] = 2
-                for coco_i, cmu_i in enumerate(sk.ORDER_COCO):
-                    if kp[coco_i, 2] > 0:
-                        j[cmu_i] = (kp[coco_i, 0], kp[coco_i, 1], 1)
-                if kp[5, 2] > 0 and kp[6, 2] > 0:
-                    j[1] = ((kp[5, 0] + kp[6, 0]) / 2, (kp[5, 1] + kp[6, 1]) / 2, 1)
-                if (j[:, 2] < 2).any():
-                    people.append(j)
-            base = synth.render_maps(np.stack(people) if people else np.zeros((0, sk.NUM_PART, 3)), hp // 4, wp // 4)
+            base = synth.render_maps(self.scene_joints(i), hp // 4, wp // 4)
             scenes.append(np.stack([base, synth.mirror_sample(base)]).astype(np.float16))
         return np.stack(scenes), {int(i): k for k, i in enumerate(indices)}
 
@@ -245,13 +260,15 @@ class DirSource:
 
 
 class SyntheticSource:
-    """Random uint8 images; image i shows scene (i mod 64) of its bucket shape with people[i mod len(people)] persons."""
+    """Random uint8 images; image i shows scene (i mod 64) of its bucket shape with people[i mod len(people)] persons -- or,
+    with per_image (--scenes device), its OWN scene: seed 20_000 + i, people[i mod len(people)] persons."""
 
-    def __init__(self, n, sizes, people):
+    def __init__(self, n, sizes, people, noise=0.02, per_image=False):
         self.n, self.sizes, self.people = n, sizes, people
+        self.scene_noise, self.per_image = float(noise), bool(per_image)
         self.image_ids = list(range(n))
         self.gts, self.has_scenes = {}, True
-        self._scenes = {}
+        self._scenes, self._joints = {}, {}
 
     def __len__(self):
         return self.n
@@ -265,7 +282,24 @@ class SyntheticSource:
         return np.frombuffer(rng.bytes(h * w * 3), np.uint8).reshape(h, w, 3)
 
     def scene_slot(self, i):
-        return i % SCENE_BANK
+        return i if self.per_image else i % SCENE_BANK
+
+    def joints(self, slot, hp, wp):
+        """ground-truth joints (P, 18, 3) of scene `slot` at padded shape (hp, wp): the people scene() renders, without
+        rendering them (synth.make_scene draws them first from the same generator)"""
+        key = (slot, hp, wp)
+        if key not in self._joints:
+            self._joints[key] = synth.random_people(self.n_people(slot), np.random.default_rng(20_000 + slot), img_h=hp, img_w=wp)
+        return self._joints[key]
+
+    def scene_joints(self, i, hp, wp):
+        return self.joints(self.scene_slot(i), hp, wp)
+
+    def max_people(self, indices):
+        return max(list(self.people) + [1])
+
+    def distinct_scenes(self, device):
+        return self.n if device else len({(self.scene_slot(i), padded_shape(*self.shape(i))) for i in range(self.n)})
 
     def bank_for_bucket(self, hp, wp, indices):
         return np.stack([self.scene(s, hp, wp)[0] for s in range(SCENE_BANK)]), {int(i): self.scene_slot(int(i)) for i in indices}
@@ -277,7 +311,8 @@ class SyntheticSource:
         """(network-output-shaped scene, ground-truth joints) of bank slot `slot` at padded shape (hp, wp)"""
         key = (slot, hp, wp)
         if key not in self._scenes:
-            self._scenes[key] = synth.make_scene(self.n_people(slot), 20_000 + slot, h=hp // 4, w=wp // 4, dtype=np.float16)
+            self._scenes[key] = synth.make_scene(self.n_people(slot), 20_000 + slot, h=hp // 4, w=wp // 4, noise=self.scene_noise,
+                                                 dtype=np.float16)
         return self._scenes[key]
 
 
@@ -290,9 +325,19 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
     shapes = [src.shape(int(i)) for i in mine]
     groups = buckets_by_padded_shape(shapes)
     max_hw = (max([padded_shape(*s)[0] for s in shapes] + [64]), max([padded_shape(*s)[1] for s in shapes] + [64]))
+    device_scenes = src.has_scenes and a.scenes == "device"
+    scene_kw = {}
+    if device_scenes:   # every image's scene is rendered from its joint list inside the batch's graph: no bank
+        from posepaf import synth_device
+        most = src.max_people([int(i) for i in mine])
+        if most > synth_device.MAX_PEOPLE:
+            raise SystemExit(f"--scenes device renders at most {synth_device.MAX_PEOPLE} people per image, an image here has {most}: "
+                             "use --scenes bank")
+        scene_kw = dict(scenes="device", max_people=most, scene_noise=src.scene_noise, scene_seed=SCENE_SEED)
     eng = InferenceEngine(model, post, B, dev.index, rules="cpp" if a.run_cpp else "py", use_graph=not a.no_graph,
                           inject_scale=1e-3 if src.has_scenes else None, max_image_hw=max_hw, render=bool(a.render_dir),
-                          progress=(lambda m: print(f"[evaluate] {m}", file=sys.stderr, flush=True)) if rank == 0 else None)
+                          progress=(lambda m: print(f"[evaluate] {m}", file=sys.stderr, flush=True)) if rank == 0 else None,
+                          **scene_kw)
     jobs = []
     for (hp, wp), members in groups.items():
         for b0 in range(0, len(members), B):
@@ -300,7 +345,7 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
             jobs.append((eng.plan(hp, wp, B if len(loc) == B else plan_batch(len(loc), B)), loc))
     # untimed set-up: scene banks, kernel choice per layer shape (rank 0 tunes, the others take its table), graph capture
     bank_slot = {}
-    if src.has_scenes:
+    if src.has_scenes and not device_scenes:
         banks = {}
         for (hp, wp), members in groups.items():
             arr, where = src.bank_for_bucket(hp, wp, [int(mine[k]) for k in members])
@@ -323,13 +368,20 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
         fused_model.save_table()
     local = torch.zeros((max(len(mine), 1), RECORD_BYTES), dtype=torch.uint8, device=dev)
 
-    def fill(k_local, j, sizes, idx, imgs):
+    def fill(k_local, j, sizes, idx, imgs, n_people=None, joints=None):
         i = int(mine[k_local])
         im = src.load(i)
         h, w = im.shape[:2]
         imgs[j, :h, :w] = im
         sizes[0, j], sizes[1, j] = h, w
-        if src.has_scenes:
+        if device_scenes:   # the image's own people travel with it; its index in the set keys the noise
+            pj = src.scene_joints(i, *padded_shape(h, w))
+            p = pj.shape[0]
+            joints[j, :p] = pj
+            joints[j, p:, :, 2] = 2
+            n_people[j] = p
+            idx[j] = i
+        elif src.has_scenes:
             idx[j] = bank_slot[i]
 
     workers = a.workers or max(1, min(16, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 8) // max(1, min(world, 8))))
@@ -360,6 +412,9 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
             "conv_table": fused_model.table_hash(), "launch": "eager" if a.no_graph else "hipGraph replay"}
     if a.render_dir:
         info["rendered_files"] = n_rendered
+    if src.has_scenes:
+        info["scenes"] = "device" if device_scenes else "bank"
+        info["distinct_scenes"] = src.distinct_scenes(device_scenes)
     if a.run_cpp:   # where pp_process_batch kept the maps it was handed (dtype and shape of each bucket's network output)
         kinds = {post.map_residency(p.maps.dtype, p.maps.shape[3], p.maps.shape[4]) for p in eng.plans.values() if p.maps is not None}
         if kinds:
@@ -408,7 +463,8 @@ def run_original(a, src, mine, model, post, dev):
 
     def scene_bank(H, W, fh, fw, sc, ang):
         entry = (fh, fw, float(sc)) if ang == 0.0 else (fh, fw, float(sc), ang)
-        return np.stack([synth.make_scene_at_scales(src.n_people(s_), 20_000 + s_, [entry], img=H)[0][0]
+        return np.stack([synth.make_scene_at_scales(src.n_people(s_), 20_000 + s_, [entry], noise=getattr(src, "scene_noise", 0.02),
+                                                    img=H)[0][0]
                          for s_ in range(SCENE_BANK)])
 
     def setup_exact(H, W):   # convolution shapes of every scale, scene banks of one image size
@@ -573,7 +629,7 @@ def ground_truth_of(src, indices, original):
         for i in indices:
             slot = src.scene_slot(i)
             joints = synth.make_scene_at_scales(src.n_people(slot), 20_000 + slot, [(8, 8, 1.0)], img=src.shape(i)[0])[1] \
-                if original else src.scene(slot, *padded_shape(*src.shape(i)))[1]
+                if original else src.joints(slot, *padded_shape(*src.shape(i)))
             gts[src.image_ids[i]] = oks_eval.gt_from_synth_joints(joints)
     return gts
 
@@ -703,6 +759,11 @@ def main(argv=None):
     if a.render_dir is not None and original:
         raise SystemExit("--render_dir draws from the records of the refactored path only (add --run_refactor): the original "
                          "path's ellipse / alpha-blend drawing (demo_image.py:218-240) stays on NumPy in demo_image.py")
+    if a.scenes == "device" and original:
+        raise SystemExit("--scenes device renders one scene per image for the refactored path only (add --run_refactor): the "
+                         "original path injects at several scales and angles and keeps its scene banks")
+    if a.scenes == "device" and not (a.inject_gt or not (a.ann_file or a.images)):
+        raise SystemExit("--scenes device needs scenes to render: --synthetic N, or --ann_file with --inject_gt")
     if a.render_limbs_dir is not None and not original:
         raise SystemExit("--render_limbs_dir draws from the records of the original path only (drop --run_refactor): the "
                          "refactored path draws its own style with --render_dir")
@@ -743,7 +804,7 @@ def main(argv=None):
         src = DirSource(a.images, a.limit)
     else:
         sizes = [tuple(int(v) for v in t.lower().split("x")) for t in a.sizes.split(",")]
-        src = SyntheticSource(a.limit or a.synthetic, sizes, a.people)
+        src = SyntheticSource(a.limit or a.synthetic, sizes, a.people, noise=a.scene_noise, per_image=a.scenes == "device")
     n_images = len(src)
     if n_images == 0:
         raise SystemExit("nothing to evaluate: pass --ann_file F --img_dir D, --images DIR or --synthetic N")
@@ -804,7 +865,7 @@ def main(argv=None):
             if src.has_scenes and not src.gts:
                 slot = src.scene_slot(i)
                 joints = synth.make_scene_at_scales(src.n_people(slot), 20_000 + slot, [(8, 8, 1.0)], img=src.shape(i)[0])[1] \
-                    if original else src.scene(slot, *padded_shape(*src.shape(i)))[1]
+                    if original else src.joints(slot, *padded_shape(*src.shape(i)))
                 gts[src.image_ids[i]] = oks_eval.gt_from_synth_joints(joints)
         os.makedirs(os.path.dirname(os.path.abspath(a.dump_name)), exist_ok=True)
         with open(a.dump_name, "w") as f:

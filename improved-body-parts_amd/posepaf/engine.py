@@ -5,7 +5,8 @@ evaluate.py:235-280), so the number the benchmark reports is the speed of the lo
 
     pinned host slot --(copy stream, H2D)--> staging ring --(HBM -> HBM)--> the plan's input buffer
         --> [HIP graph of the plan: pad / 255 / mirror (pp_preprocess_u8_ragged) -> IMHN forward (fp16) ->
-             (synthetic runs only: + scene bank[idx]) -> K_A -> K_B (+ assembly)
+             (synthetic runs only: + scene bank[idx], or with scenes="device" + the scenes pp_render_scenes draws from
+              the batch's own joint lists) -> K_A -> K_B (+ assembly)
              (render=True only: -> pp_draw_humans_u8, the skeletons on the plan's canvas)] --> pp_record[b] of the plan
 
 A *plan* belongs to one bucket `(Hp, Wp, b)`: `b` images whose sizes pad to the same multiple-of-64 shape
@@ -43,6 +44,12 @@ def header_bytes(b: int) -> int:
     return -(-(16 * b) // 256) * 256
 
 
+def scene_bytes(b: int, max_people: int) -> int:
+    """scenes="device" only, after the images: int32 n_people[b], float32 joints[b][max_people][18][3] (the header's bank_idx
+    field carries the scene ids)"""
+    return 4 * b + 4 * b * max_people * sk.NUM_PART * 3
+
+
 class Slot:
     """One pinned host batch: header (sizes, bank indices) followed by the images of a (b, Hp, Wp, 3) bucket."""
 
@@ -64,16 +71,24 @@ class Slot:
         imgs = self.np[hb: hb + b * hp * wp * 3].reshape(b, hp, wp, 3)
         return sizes, idx, imgs
 
+    def scene_views(self, b: int, hp: int, wp: int, max_people: int):
+        """scenes="device": -> (n_people int32 (b,), joints float32 (b, max_people, 18, 3)) numpy views of the pinned bytes
+        behind the images; the scene ids travel in views()' int64 field"""
+        at = header_bytes(b) + b * hp * wp * 3
+        n_people = self.np[at: at + 4 * b].view(np.int32)
+        joints = self.np[at + 4 * b: at + scene_bytes(b, max_people)].view(np.float32).reshape(b, max_people, sk.NUM_PART, 3)
+        return n_people, joints
+
 
 class _Plan:
     def __init__(self, eng, hp: int, wp: int, b: int):
         dev = eng.dev
         self.hp, self.wp, self.b = hp, wp, b
-        self.nbytes = header_bytes(b) + b * hp * wp * 3
+        self.nbytes = header_bytes(b) + b * hp * wp * 3 + eng._scene_bytes(b)
         self.flat = torch.zeros(self.nbytes, dtype=torch.uint8, device=dev)
         self.sizes = self.flat[: 8 * b].view(torch.int32).view(2, b)
         self.bank_idx = self.flat[8 * b: 16 * b].view(torch.int64)
-        self.images = self.flat[header_bytes(b):].view(b, hp, wp, 3)
+        self.images = self.flat[header_bytes(b): header_bytes(b) + b * hp * wp * 3].view(b, hp, wp, 3)
         self.sizes[0].fill_(hp)
         self.sizes[1].fill_(wp)
         self.records = torch.zeros(b * RECORD_BYTES, dtype=torch.uint8, device=dev)
@@ -82,6 +97,13 @@ class _Plan:
         self.maps = None              # the plan's last network output (kept for checks)
         # render=True: the images of the batch with their skeletons drawn (each image's own corner; valid until the next submit)
         self.canvas = torch.zeros((b, hp, wp, 3), dtype=torch.uint8, device=dev) if eng.render else None
+        self.n_people = self.joints = self.scenes = None
+        if eng.scenes == "device":   # the batch's joint lists (uploaded with the images) and the scenes rendered from them
+            at = header_bytes(b) + b * hp * wp * 3
+            self.n_people = self.flat[at: at + 4 * b].view(torch.int32)
+            self.joints = self.flat[at + 4 * b:].view(torch.float32).view(b, eng.max_people, sk.NUM_PART, 3)
+            self.joints[..., 2] = 2
+            self.scenes = torch.zeros((b, 2, sk.NUM_CH, hp // 4, wp // 4), dtype=torch.float16, device=dev)
 
 
 class InferenceEngine:
@@ -89,12 +111,18 @@ class InferenceEngine:
     rules: "cpp" = pafprocess rules (evaluate.py --run_cpp), "py" = find_connections + find_humans rules.
     inject_scale: synthetic runs add scene_bank[idx] to `inject_scale * network output` (a randomly initialised network emits
     no peaks); None = the network output alone (real weights).
+    scenes: where a synthetic run's scenes come from.  "bank" (default): set_bank() + slot bank_idx, as ever.  "device": a slot
+    also carries the joints (b, max_people, 18, 3) and people counts of its images (Slot.scene_views) and their scene ids (the
+    int64 header field); the plan renders them into a tensor of its own inside the captured graph (synth_device.render_scenes,
+    noise scene_noise keyed by scene_seed and the scene id) and adds `inject_scale * network output` exactly as the bank path
+    does after index_select.  No bank, nothing kept per image.
     render: every plan also owns `canvas`, a (b, hp, wp, 3) uint8 device buffer, and the per-batch path ends with the skeletons
     of the plan's records drawn from its images into that canvas (posepaf.render.draw_records, inside the captured graph)."""
 
     def __init__(self, model, post, batch: int, device: int, rules: str = "cpp", use_graph: bool = True,
                  inject_scale: float | None = None, max_image_hw=(512, 512), n_slots: int = 3, n_staging: int = 2,
-                 postproc_only: bool = False, progress=None, render: bool = False):
+                 postproc_only: bool = False, progress=None, scenes: str = "bank", max_people: int = 16,
+                 scene_noise: float = 0.0, scene_seed: int = 0, render: bool = False):
         if not torch.cuda.is_available():
             raise PosePafError("no HIP device: the engine has no CPU path")
         if rules not in ("cpp", "py"):
@@ -103,9 +131,19 @@ class InferenceEngine:
         self.dev = torch.device("cuda", device)
         self.use_graph, self.postproc_only, self.progress = use_graph, postproc_only, progress
         self.render = bool(render)
+        if scenes not in ("bank", "device"):
+            raise PosePafError(f"scenes must be 'bank' or 'device', got {scenes!r}")
+        self.scenes, self.max_people = scenes, int(max_people)
+        self.scene_noise, self.scene_seed = float(scene_noise), int(scene_seed)
+        if scenes == "device":
+            from .synth_device import MAX_PEOPLE
+            if not 1 <= self.max_people <= MAX_PEOPLE:
+                raise PosePafError(f"max_people must be in 1..{MAX_PEOPLE}, got {max_people}")
+            if inject_scale is None and not postproc_only:
+                raise PosePafError("scenes='device' injects into the network output: pass inject_scale")
         self.inject_scale = None if inject_scale is None else torch.tensor(inject_scale, dtype=torch.float16, device=self.dev)
         hp, wp = padded_shape(*max_image_hw)
-        self.max_bytes = header_bytes(self.B) + self.B * hp * wp * 3
+        self.max_bytes = header_bytes(self.B) + self.B * hp * wp * 3 + self._scene_bytes(self.B)
         self.copy_stream = torch.cuda.Stream(device=self.dev)
         self.staging = [torch.empty(self.max_bytes, dtype=torch.uint8, device=self.dev) for _ in range(n_staging)]
         self.consumed = [torch.cuda.Event() for _ in range(n_staging)]
@@ -118,13 +156,16 @@ class InferenceEngine:
         self.n_submit = 0
         self._lock = threading.Lock()
 
+    def _scene_bytes(self, b: int) -> int:
+        return scene_bytes(b, self.max_people) if self.scenes == "device" else 0
+
     # ------------------------------------------------------------------ plans
     def plan(self, hp: int, wp: int, b: int | None = None) -> _Plan:
         b = self.B if b is None else int(b)
         key = (hp, wp, b)
         p = self.plans.get(key)
         if p is None:
-            if b > self.B or header_bytes(b) + b * hp * wp * 3 > self.max_bytes:
+            if b > self.B or header_bytes(b) + b * hp * wp * 3 + self._scene_bytes(b) > self.max_bytes:
                 raise PosePafError(f"bucket {key} exceeds the engine's slot size (batch {self.B}, {self.max_bytes} bytes)")
             p = self.plans[key] = _Plan(self, hp, wp, b)
         return p
@@ -134,6 +175,8 @@ class InferenceEngine:
         bank of this plan (before prepare())"""
         if plan.graph is not None:
             raise PosePafError("set_bank() after prepare(): the bank is part of the captured graph")
+        if self.scenes == "device":
+            raise PosePafError("set_bank() on an engine with scenes='device': the scenes are rendered from the slot's joints")
         want = (2, sk.NUM_CH, plan.hp // 4, plan.wp // 4)
         if isinstance(scenes, np.ndarray):
             scenes = torch.from_numpy(np.ascontiguousarray(scenes))
@@ -145,8 +188,12 @@ class InferenceEngine:
         import ctypes as C
         from . import _lib
         b, hp, wp = p.b, p.hp, p.wp
+        if self.scenes == "device":
+            from .synth_device import render_scenes
+            render_scenes(p.joints, p.n_people, hp // 4, wp // 4, torch.float16, flip=True, noise=self.scene_noise,
+                          seed=self.scene_seed, scene_ids=p.bank_idx, out=p.scenes)
         if self.postproc_only:
-            maps = p.bank.index_select(0, p.bank_idx)
+            maps = p.scenes if self.scenes == "device" else p.bank.index_select(0, p.bank_idx)
         else:
             x = torch.empty((2 * b, hp, wp, 3), dtype=torch.float16, device=self.dev)
             _lib.check(_lib.load().pp_preprocess_u8_ragged(
@@ -155,7 +202,9 @@ class InferenceEngine:
             out = self.model(x)
             out = out[-1][0] if isinstance(out, (list, tuple)) else out
             maps = to_planes(out).view(b, 2, sk.NUM_CH, hp // 4, wp // 4)
-            if p.bank is not None:
+            if self.scenes == "device":
+                maps = torch.addcmul(p.scenes, maps, self.inject_scale)
+            elif p.bank is not None:
                 maps = torch.addcmul(p.bank.index_select(0, p.bank_idx), maps, self.inject_scale)
         p.maps = maps
         heights = p.sizes[0]
@@ -234,7 +283,8 @@ class InferenceEngine:
 class BatchFeeder:
     """Background loader: `depth` producer threads fill pinned slots (each image of a batch by a pool of `workers` decode
     threads) and hand (job, slot) pairs to the engine thread.  jobs: list of (plan, [items]); fill(item, j, sizes, idx, imgs)
-    writes item j of the batch into the slot views."""
+    writes item j of the batch into the slot views.  On an engine with scenes="device" fill also receives the slot's
+    (n_people, joints) views: fill(item, j, sizes, idx, imgs, n_people, joints); unused entries hold no people."""
 
     def __init__(self, engine: InferenceEngine, jobs, fill, workers: int = 8, depth: int = 2):
         from concurrent.futures import ThreadPoolExecutor
@@ -265,7 +315,12 @@ class BatchFeeder:
                 sizes[0, :] = plan.hp        # unused tail entries of a short batch: a blank full-size image, bank scene 0
                 sizes[1, :] = plan.wp
                 idx[:] = 0
-                list(self.pool.map(lambda t: self.fill(t[1], t[0], sizes, idx, imgs), enumerate(items)))
+                if self.eng.scenes == "device":
+                    extra = slot.scene_views(plan.b, plan.hp, plan.wp, self.eng.max_people)
+                    extra[0][:] = 0
+                    list(self.pool.map(lambda t: self.fill(t[1], t[0], sizes, idx, imgs, *extra), enumerate(items)))
+                else:
+                    list(self.pool.map(lambda t: self.fill(t[1], t[0], sizes, idx, imgs), enumerate(items)))
                 self.out.put((j, slot))
         except BaseException as e:   # surfaced by the consumer
             self.error = e

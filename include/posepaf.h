@@ -426,6 +426,31 @@ PP_API int pp_oks_match(const float *rows_dev, const int *counts_dev, int batch,
                         const double *area_ranges, int *order_dev, float *scores_dev, signed char *match_dev, int *n_det_dev,
                         int *n_gt_dev, double *oks_dev, void *stream);
 
+/* Ground-truth-style scenes in the network-output layout, rendered on the device from joint lists (the reference's training-target
+ * recipe, py_cocodata_server/py_data_heatmapper.py:105-257; csrc/posepaf_synth.hip spells out the arithmetic): what synthetic
+ * evaluations inject into the network output.  Needs no context.
+ *   joints_dev   DEVICE float[batch][max_people][18][3]: x, y in image pixels (stride 4: map cell i sits at 4 i + 1.5) and a flag,
+ *                flag < 2 = annotated; n_people_dev: DEVICE int[batch], clamped to [0, max_people]; people past it are never read
+ *   scene_id_dev DEVICE long long[batch], the noise identity of each image (NULL: the image's index); unused without noise
+ *   out_dev      DEVICE (batch, n_samples, 50, h, w) planar, dtype PP_F16 or PP_F32; every word is stored on every launch.
+ *                n_samples = 2 adds the mirrored sample, out1[c][y][x] = out0[flip_ord[c]][y][w - 1 - x] (config/config.py:150-152)
+ *   flags        PP_SCENE_REVERSE_KP: channel 49 = max over the keypoint channels 30..47 (:86); other bits are reserved and ignored.
+ *                Channel 48 (the segmentation mask of the reference) is always zero
+ *   noise_sigma  > 0: sigma * N(0, 1) added after the clip to [0, 1], no second clip.  Counter-based (Philox4x32-10 keyed by seed,
+ *                counter = scene id, sample, channel, pixel; Box-Muller in float32): an image gets the same noise in whichever
+ *                batch, slot or launch geometry it is rendered
+ * Deterministic (gather, no atomics; people are accumulated in index order).  PP_ERR_BAD_ARG: a null joints / n_people / out
+ * pointer, n_samples outside {1, 2}, a dtype that is neither PP_F16 nor PP_F32, a non-positive batch / max_people / h / w, a
+ * negative or NaN noise_sigma.  PP_ERR_UNSUPPORTED: max_people above PP_SCENE_MAX_PEOPLE (the joints and windows of one image are
+ * staged in LDS and its people are compacted by one wave).  PP_ERR_TOO_LARGE: batch above 65535, a map side above 10^6, or 2^24 or
+ * more 64 x 32 tiles in one map.
+ * PP_ERR_NO_DEVICE without a HIP device.  Asynchronous, nothing allocated: capturable. */
+#define PP_SCENE_REVERSE_KP 1
+#define PP_SCENE_MAX_PEOPLE 64
+PP_API int pp_render_scenes(const float *joints_dev, const int *n_people_dev, const long long *scene_id_dev, int batch,
+                            int max_people, int h, int w, int n_samples, int dtype, int flags, float noise_sigma,
+                            unsigned long long seed, void *out_dev, void *stream);
+
 /* A2 standalone: the arrays predict_refactor returns (utils/parse_skeletons.py:82-103).  net_out_dev as for
  * pp_process_batch; heat_hwc_dev: DEVICE float[batch][h][w][20], paf_hwc_dev: DEVICE float[batch][h][w][30]. */
 PP_API int pp_flip_average(const void *net_out_dev, int dtype, int batch, int h, int w, int flip, float *heat_hwc_dev,
