@@ -15,6 +15,8 @@
         that pad alike at every scale share one ragged bucket (POSEPAF_ORIGINAL_BUCKETS=exact: group by exact size instead)
     python evaluate.py --run_refactor --run_cpp --synthetic 5000 --scenes device     # 5000 distinct scenes, each rendered on the
         GPU from its joint list inside the batch's graph (default --scenes bank: 64 host-rendered scenes, image i shows i mod 64)
+    python evaluate.py --val_loss --synthetic 512 --batch 32                         # the reference's validation loss (multi-scale
+        focal L2 over 4 stacks x 5 scales, models/loss_model.py) of the fused model against device-rendered targets, per stack / scale
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --synthetic 5000 ...
 
 What is kept from the reference: the flags --run_refactor / --run_cpp (:53-54; --run_cpp selects the C++ pafprocess rules --
@@ -121,7 +123,15 @@ def parse(argv=None):
                          "the result rows and matches them against its shard's ground truth on its own GPU (pp_coco_rows_f32, "
                          "pp_oks_match), rank 0 accumulates; host: rank 0 does all of it in Python.  Without the option the report "
                          "is evaluate_keypoints' (range `all` only), as before")
-    ap.add_argument("--scenes", choices=("bank", "device"), default="bank",
+    ap.add_argument("--val_loss", action="store_true",
+                    help="a mode of its own: the reference's validation loss (MultiTaskLoss.focal_l2_loss over every stack and scale, "
+                         "models/loss_model.py:23-81, :133-161; train*.py test()) of the fused model, computed on the device "
+                         "(pp_focal_l2_terms).  Per batch: pad / normalise as the refactored path does, model(x, all_preds=True), the "
+                         "targets rendered on the device from the image's own joints (--synthetic: its people; --ann_file: its "
+                         "annotations) with reverse_kp and no noise, mask of ones (mask_miss needs crowd segmentations).  Takes "
+                         "--batch, --sizes, --arch, -p; prints one JSON line.  Refuses --scales, --rotation_search, --test_cfg, "
+                         "--config_file, --render_dir, --render_limbs_dir, --ap and --scenes bank")
+    ap.add_argument("--scenes", choices=("bank", "device"), default=None,
                     help="where the injected scenes (--synthetic, --inject_gt) come from.  bank: rendered on the host before the "
                          "run and kept in HBM -- 64 per bucket shape for --synthetic (image i shows scene i mod 64), one per image "
                          "for --inject_gt.  device (with --run_refactor): every image's own scene, rendered from its joint list "
@@ -131,6 +141,7 @@ def parse(argv=None):
                     help="--synthetic: sigma of the noise added to the injected scenes (both --scenes modes; the device renderer "
                          "draws it from a counter-based generator, so the two modes' noise values differ)")
     a = ap.parse_args(argv)
+    a.scenes_given, a.scenes = a.scenes, a.scenes or "bank"
     if a.scene_noise < 0:
         ap.error("--scene_noise must be >= 0")
     a.test_cfg_dict = None
@@ -618,6 +629,71 @@ def run_original(a, src, mine, model, post, dev):
     return local.view(-1), time.perf_counter() - t0, info
 
 
+# ------------------------------------------------------------------------------------------------ --val_loss
+def val_loss_conflicts(a):
+    """the options --val_loss cannot be combined with, as the user typed them"""
+    named = (("--scales", a.scales is not None), ("--rotation_search", a.rotation_search is not None),
+             ("--test_cfg", a.test_cfg is not None), ("--config_file", a.config_file is not None),
+             ("--render_dir", a.render_dir is not None), ("--render_limbs_dir", a.render_limbs_dir is not None),
+             ("--ap", a.ap is not None), ("--scenes bank", a.scenes_given == "bank"), ("--images", a.images is not None),
+             ("--inject_gt", a.inject_gt), ("--gpus", a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1))
+    return [name for name, given in named if given]
+
+
+def run_val_loss(a, src, model, dev):
+    """--val_loss: every image through model(x, all_preds=True) and pp_focal_l2_terms against its own device-rendered target.
+    -> the meter's summary + seconds (set-up -- tuning the layer shapes of every bucket -- excluded)"""
+    import ctypes as C
+    from posepaf import _lib, synth_device, val_loss
+    L = _lib.load()
+    B = a.batch
+    shapes = [src.shape(i) for i in range(len(src))]
+    groups = buckets_by_padded_shape(shapes)
+    most = src.max_people(range(len(src)))
+    if most > synth_device.MAX_PEOPLE:
+        raise SystemExit(f"--val_loss renders at most {synth_device.MAX_PEOPLE} people per image, an image here has {most}")
+    meter = val_loss.ValLossMeter()
+
+    def preprocess(staged, sizes):
+        n, hp, wp, _ = staged.shape
+        x = torch.empty((n, hp, wp, 3), dtype=torch.float16, device=dev)
+        _lib.check(L.pp_preprocess_u8_ragged(C.c_void_p(staged.data_ptr()), C.c_void_p(sizes.data_ptr()), C.c_void_p(x.data_ptr()),
+                                             _lib.PP_F16, n, hp, wp, sk.PAD_VALUE, 0,
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return x
+
+    with torch.no_grad():
+        for (hp, wp), members in groups.items():   # untimed: the kernel choice of every layer shape this bucket runs
+            model(torch.zeros((B, hp, wp, 3), dtype=torch.float16, device=dev), all_preds=True)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for (hp, wp), members in groups.items():
+            for b0 in range(0, len(members), B):
+                loc = members[b0:b0 + B]
+                n = len(loc)                             # a short last batch repeats its first image in the unused slots: one
+                loc = loc + [loc[0]] * (B - n)           # batch size per bucket to tune, and the meter counts the first n only
+                imgs = np.full((B, hp, wp, 3), sk.PAD_VALUE, np.uint8)
+                sizes = np.zeros((2, B), np.int32)
+                people = []
+                for j, i in enumerate(loc):
+                    im = src.load(i)
+                    h, w = im.shape[:2]
+                    imgs[j, :h, :w] = im
+                    sizes[0, j], sizes[1, j] = h, w
+                    people.append(src.scene_joints(i, hp, wp))
+                joints, n_people = synth_device.pack_joints(people, most)
+                x = preprocess(torch.from_numpy(imgs).to(dev), torch.from_numpy(sizes).to(dev))
+                preds = model(x, all_preds=True)
+                target = synth_device.render_scenes(torch.from_numpy(joints).to(dev), torch.from_numpy(n_people).to(dev), hp // 4, wp // 4,
+                                                    dtype=torch.float16, flip=False, noise=0.0, reverse_kp=True)
+                meter.update(val_loss.focal_l2_terms(preds, target), n_valid=n)
+        torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+    out = meter.summary()
+    out.update({"seconds": dt, "mask_miss": "none", "images_per_step": B, "padded_shapes": sorted(groups)})
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ --ap host / device
 def ground_truth_of(src, indices, original):
     """Ground truth of the images `indices`, as the default report derives it: from the annotation file, or from the injected
@@ -732,6 +808,15 @@ def report_with_ap(a, src, merged, summary, gathered, original):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse(argv)
+    if a.val_loss:   # a mode of its own: refused combinations leave before anything touches the GPU
+        bad = val_loss_conflicts(a)
+        if bad:
+            raise SystemExit("--val_loss is a mode of its own (the fused model's multi-scale focal-L2 loss against device-rendered "
+                             "targets, one process) and does not combine with " + ", ".join(bad))
+        if not (a.ann_file or a.synthetic or a.limit):
+            raise SystemExit("--val_loss needs images with joints: --synthetic N, or --ann_file F --img_dir D")
+        if a.ann_file and not a.img_dir:
+            raise SystemExit("--ann_file needs --img_dir")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:   # before anything touches the GPU; children are started, never exec'd
         import socket
         import subprocess
@@ -759,10 +844,10 @@ def main(argv=None):
     if a.render_dir is not None and original:
         raise SystemExit("--render_dir draws from the records of the refactored path only (add --run_refactor): the original "
                          "path's ellipse / alpha-blend drawing (demo_image.py:218-240) stays on NumPy in demo_image.py")
-    if a.scenes == "device" and original:
+    if a.scenes == "device" and original and not a.val_loss:
         raise SystemExit("--scenes device renders one scene per image for the refactored path only (add --run_refactor): the "
                          "original path injects at several scales and angles and keeps its scene banks")
-    if a.scenes == "device" and not (a.inject_gt or not (a.ann_file or a.images)):
+    if a.scenes == "device" and not a.val_loss and not (a.inject_gt or not (a.ann_file or a.images)):
         raise SystemExit("--scenes device needs scenes to render: --synthetic N, or --ann_file with --inject_gt")
     if a.render_limbs_dir is not None and not original:
         raise SystemExit("--render_limbs_dir draws from the records of the original path only (drop --run_refactor): the "
@@ -804,11 +889,16 @@ def main(argv=None):
         src = DirSource(a.images, a.limit)
     else:
         sizes = [tuple(int(v) for v in t.lower().split("x")) for t in a.sizes.split(",")]
-        src = SyntheticSource(a.limit or a.synthetic, sizes, a.people, noise=a.scene_noise, per_image=a.scenes == "device")
+        src = SyntheticSource(a.limit or a.synthetic, sizes, a.people, noise=a.scene_noise, per_image=a.scenes == "device" or a.val_loss)
     n_images = len(src)
     if n_images == 0:
         raise SystemExit("nothing to evaluate: pass --ann_file F --img_dir D, --images DIR or --synthetic N")
 
+    if a.val_loss:
+        summary = run_val_loss(a, src, model, dev)
+        summary["arch"] = a.arch
+        print(json.dumps(summary))
+        return 0
     scales = a.scales or [1.0]
     mine = pdist.shard_indices(n_images, rank, world)
     S = pdist.padded_shard_size(n_images, world)

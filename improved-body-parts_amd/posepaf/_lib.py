@@ -32,6 +32,7 @@ GT_ANN_DTYPE = np.dtype([("keypoints", "<f8", (17, 3)), ("area", "<f8"), ("bbox"
                          ("num_keypoints", "<i4"), ("has_bbox", "<i4"), ("reserved", "<i4")])
 COCO_ROW, AP_MAX_DETS, AP_MAX_GT, AP_THRESHOLDS, AP_RANGES = 52, 20, 128, 10, 3
 SCENE_REVERSE_KP, SCENE_MAX_PEOPLE = 1, 64        # pp_render_scenes (include/posepaf.h)
+LOSS_PLAIN_L2, LOSS_MAX_STACKS, LOSS_MAX_SCALES = 1, 8, 5   # pp_focal_l2_terms (include/posepaf.h)
 
 EXPORTS = [
     "pp_create", "pp_destroy", "pp_last_hip_error", "pp_status_string", "pp_device_available", "pp_process_batch", "pp_process_batch_py",
@@ -43,7 +44,7 @@ EXPORTS = [
     "pp_default_test_cfg", "pp_set_test_cfg", "pp_get_test_cfg",
     "pp_set_map_residency", "pp_map_residency", "pp_map_workspace_bytes", "pp_time_map_prepass", "pp_draw_humans_u8",
     "pp_draw_limbs_u8", "pp_limb_angle_table", "pp_limb_angle_deg",
-    "pp_coco_rows_f32", "pp_oks_match", "pp_render_scenes",
+    "pp_coco_rows_f32", "pp_oks_match", "pp_render_scenes", "pp_focal_l2_workspace_bytes", "pp_focal_l2_terms",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -125,6 +126,10 @@ def load():
                                vp, vp, vp, vp, vp, vp, vp]
     L.pp_render_scenes.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                    C.c_ulonglong, vp, vp]
+    L.pp_focal_l2_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip]
+    L.pp_focal_l2_workspace_bytes.restype = C.c_longlong
+    L.pp_focal_l2_terms.argtypes = [C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, ip, ip, C.c_double, C.c_double, C.c_int, vp, vp, vp]
     L.pp_flip_average.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_pwconv_supported.argtypes = [C.c_int, C.c_int]
     L.pp_pwconv_f16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int, vp]

@@ -10,6 +10,8 @@ Only the 7x7 stride-2 stem and the 50-channel heads stay on PyTorch-ROCm (MIOpen
   * BN (eval) folded:  w' = w * g / sqrt(var + eps),  b' = beta - mean * g / sqrt(var + eps)
   * only `[-1][0]` (last stage, full-resolution scale) is produced -- the sole output the inference path reads
     (utils/parse_skeletons.py:80); the last stage's coarse-scale feature/pred heads feed nothing and are skipped
+    (forward(all_preds=True) computes all of the reference's pred[t][s] in addition: what the validation loss scores,
+    posepaf/val_loss.py)
   * LeakyReLU applied in place on the conv output
 
 `FusedIMHN.from_network(NetworkEval)` takes the weights of the checkpoint-compatible definition in
@@ -1119,8 +1121,11 @@ class FusedIMHN(nn.Module):
                 return FusedIMHNFinal(net)
         return cls(net)
 
-    def forward(self, imgs, stage_preds: bool = False):
-        """stage_preds=True (tests): -> the scale-0 prediction of EVERY stage, i.e. the reference's out[t][0] for t = 0..S-1."""
+    def forward(self, imgs, stage_preds: bool = False, all_preds: bool = False):
+        """stage_preds=True (tests): -> the scale-0 prediction of EVERY stage, i.e. the reference's out[t][0] for t = 0..S-1.
+        all_preds=True (the validation loss): -> the reference's pred[t][s] for every stage and all K scales, a list of lists; the
+        (folded) merges drive the chain as always, the heads run in addition, the last stage's coarse scales included.  The tensors
+        are the heads' own: the [:, :50] view of a 64-channel pixel-major tensor where FHead took its fast path."""
         seen = []
         x = imgs.permute(0, 3, 1, 2)  # NHWC storage viewed as NCHW == channels_last: no copy
         x = self.stem(x)
@@ -1146,18 +1151,18 @@ class FusedIMHN(nn.Module):
         caches, x_pooled = None, None
         for t in range(self.S):
             last = t == self.S - 1
-            scales = range(1) if last else range(self.K)  # the last stage's coarse heads feed nothing
+            scales = range(1) if last and not all_preds else range(self.K)  # the last stage's coarse heads feed nothing
             hg = self.hg[t](x, None if caches is None else caches[0], x_pooled)   # scale 0 comes back with its cache added
             if caches is not None:
                 hg = [hg[0]] + [hg[s] + caches[s] for s in scales if s > 0]
             # feats[s] stays a (feature map, SE gains) pair: its consumers -- the head and the merge convolution, both 1x1 --
             # multiply while they read
             feats = [self.feat[t][s](hg[s], fold=True) for s in scales]
-            if last or stage_preds or not self.folded_merge:
-                preds = [self.head[t][s](feats[s]) for s in (scales if not self.folded_merge else range(1))]
-                seen.append(preds[0])
+            if last or stage_preds or all_preds or not self.folded_merge:
+                preds = [self.head[t][s](feats[s]) for s in (scales if all_preds or not self.folded_merge else range(1))]
+                seen.append(preds if all_preds else preds[0])
             if last:
-                return seen if stage_preds else preds[0]
+                return seen if stage_preds or all_preds else preds[0]
             if self.folded_merge:   # merge_preds(head(.)) lives inside merge_features' weights: no head, no prediction merge
                 c0, x, x_pooled = self.mfeat[t][0].forward_dual(feats[0], None, x, want_pool=True)
                 caches = [c0] + [self.mfeat[t][s](feats[s]) for s in scales if s > 0]
@@ -1243,24 +1248,27 @@ class FusedIMHNFinal(FusedIMHN):
         self.feat = nn.ModuleList([nn.ModuleList([FFeatureFinal(s) for s in f.before_regress]) for f in p.features])
         self._init_heads_and_merges(p)
 
-    def forward(self, imgs, stage_preds: bool = False):
-        """stage_preds=True (tests): -> the scale-0 prediction of EVERY stage, i.e. the reference's out[t][0] for t = 0..S-1."""
+    def forward(self, imgs, stage_preds: bool = False, all_preds: bool = False):
+        """stage_preds=True (tests): -> the scale-0 prediction of EVERY stage, i.e. the reference's out[t][0] for t = 0..S-1.
+        all_preds=True (the validation loss): -> the reference's pred[t][s] for every stage and all K scales, a list of lists; the
+        (folded) merges drive the chain as always, the heads run in addition, the last stage's coarse scales included.  The tensors
+        are the heads' own: the [:, :50] view of a 64-channel pixel-major tensor where FHead took its fast path."""
         seen = []
         x = self.stem(imgs.permute(0, 3, 1, 2))  # NHWC storage viewed as NCHW == channels_last: no copy
         x, x_pooled = self.res3.forward_pool(self.res2(self.res1.forward_pool(x)[1]))
         caches = None
         for t in range(self.S):
             last = t == self.S - 1
-            scales = range(1) if last else range(self.K)  # the last stage's coarse heads feed nothing
+            scales = range(1) if last and not all_preds else range(self.K)  # the last stage's coarse heads feed nothing
             hg = self.hg[t](x, x_pooled, scales)
             # SE(h)_s (+ cache_s) is never written: the gains and the cache enter the compress convolution's input read
             feats = [self.feat[t][s](hg[s][0], self.att[t][s].gains(hg[s][0], hg[s][1]), None if caches is None else caches[s])
                      for s in scales]
-            if last or stage_preds or not self.folded_merge:
-                preds = [self.head[t][s](feats[s]) for s in (scales if not self.folded_merge else range(1))]
-                seen.append(preds[0])
+            if last or stage_preds or all_preds or not self.folded_merge:
+                preds = [self.head[t][s](feats[s]) for s in (scales if all_preds or not self.folded_merge else range(1))]
+                seen.append(preds if all_preds else preds[0])
             if last:
-                return seen if stage_preds else preds[0]
+                return seen if stage_preds or all_preds else preds[0]
             if self.folded_merge:   # merge_preds(head(.)) lives inside merge_features' weights: no head, no prediction merge
                 c0, x, x_pooled = self.mfeat[t][0].forward_dual(feats[0], None, x, want_pool=True)
                 caches = [c0] + [self.mfeat[t][s](feats[s]) for s in scales if s > 0]

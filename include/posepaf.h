@@ -451,6 +451,41 @@ PP_API int pp_render_scenes(const float *joints_dev, const int *n_people_dev, co
                             int max_people, int h, int w, int n_samples, int dtype, int flags, float noise_sigma,
                             unsigned long long seed, void *out_dev, void *stream);
 
+/* The reference's multi-scale focal-L2 validation loss (models/loss_model.py:23-81, :133-161) as per-image terms
+ *   terms[t][s][b] = sum over c, y, x of (p - G)^2 * |1 - st| * M * cw[c]
+ * for stack t, scale s, image b (csrc/posepaf_loss.hip spells out the arithmetic): G = the target pooled to the prediction's size by
+ * adaptive_avg_pool2d's window formula (float64 sum, one rounding to float32; a window that holds nothing but 0.01f pools to exactly
+ * 0.01f), st = p where G >= 0.01f (float32 comparison) else 1 - p, M = the mask resampled bilinearly (align_corners = False) in
+ * float64 with values < 0.5 set to 0, cw = multi_task_weight for channel 48, keypoint_task_weight for channels 30..47, 1 otherwise;
+ * everything behind G and M in float64.  PP_LOSS_PLAIN_L2 drops |1 - st| (l2_loss, :103-131).  Needs no context.
+ *   pred_dev     HOST array of n_stacks * n_scales DEVICE pointers, [t * n_scales + s] -> the prediction of (batch, 50, hs[s], ws[s]);
+ *                read during the call only (the table travels by value in the kernel arguments)
+ *   pred_dtype   PP_F16 or PP_F32, of every prediction
+ *   pred_pixel_stride   0: planes (batch, 50, h_s, w_s); >= 50: pixel-major (batch, h_s, w_s, stride), channels 0..49 of a pixel read,
+ *                the rest never (64 = what the fused heads write, 50 = a channels-last tensor)
+ *   target_dev   DEVICE planes (50, H, W) per image, PP_F16 or PP_F32, target_image_stride elements (>= 50 H W) from one image to the
+ *                next: sample 0 of a (batch, 2, 50, H, W) buffer is read in place with 2 * 50 * H * W
+ *   mask_dev     DEVICE float (batch, H, W), or NULL = all ones
+ *   hs, ws       HOST int[n_scales], 1 <= hs[s] <= H, 1 <= ws[s] <= W (any sizes: the windows need not divide)
+ *   workspace_dev  DEVICE, pp_focal_l2_workspace_bytes(batch, n_stacks, n_scales, hs, ws) bytes, 8-byte aligned
+ *   terms_dev    DEVICE double[n_stacks][n_scales][batch]
+ * Every word of terms_dev and every workspace word that is read is stored plainly on every launch (no memset, no atomics).
+ * Deterministic: the order of an image's additions depends on the shapes alone -- its terms are bit-identical in every batch, slot
+ * and run.  Predictions are read with 16-byte loads where their runs are 16-byte aligned and element by element elsewhere (same
+ * order).  PP_ERR_BAD_ARG: a null pointer (but mask_dev), a pointer not aligned to its element (workspace / terms: 8 bytes), a dtype
+ * that is neither PP_F16 nor PP_F32, batch / n_stacks / n_scales / H / W < 1, an hs / ws entry outside 1..H / 1..W,
+ * pred_pixel_stride in 1..49 or negative, target_image_stride below 50 H W.  PP_ERR_UNSUPPORTED: n_stacks above 8, n_scales above 5.
+ * PP_ERR_TOO_LARGE: batch above 65535, more than 2^30 pixels in a map, a pixel stride above 2^20, 2^31 or more workgroups (128-pixel
+ * tiles of all scales x batch).  PP_ERR_NO_DEVICE without a HIP
+ * device (after the argument checks).  Asynchronous, nothing allocated: capturable.
+ * pp_focal_l2_workspace_bytes: the bytes, or the negative status of the same shape checks. */
+#define PP_LOSS_PLAIN_L2 1
+PP_API long long pp_focal_l2_workspace_bytes(int batch, int n_stacks, int n_scales, const int *hs, const int *ws);
+PP_API int pp_focal_l2_terms(const void *const *pred_dev, int pred_dtype, int pred_pixel_stride, const void *target_dev, int target_dtype,
+                             long long target_image_stride, const float *mask_dev, int batch, int H, int W, int n_stacks, int n_scales,
+                             const int *hs, const int *ws, double multi_task_weight, double keypoint_task_weight, int flags,
+                             void *workspace_dev, double *terms_dev, void *stream);
+
 /* A2 standalone: the arrays predict_refactor returns (utils/parse_skeletons.py:82-103).  net_out_dev as for
  * pp_process_batch; heat_hwc_dev: DEVICE float[batch][h][w][20], paf_hwc_dev: DEVICE float[batch][h][w][30]. */
 PP_API int pp_flip_average(const void *net_out_dev, int dtype, int batch, int h, int w, int flip, float *heat_hwc_dev,
