@@ -24,9 +24,8 @@ struct pp_ctx {
     float4 *d_conns = nullptr;    // [max_batch][30][maxp] (cid1 bits, cid2 bits, score, length)
     int *d_conn_counts = nullptr; // [max_batch][30]
     float4 *d_conn_aux = nullptr; // [max_batch][30][maxp] (peak id 1, peak id 2, peak score 1, peak score 2): K_B -> assembly
-    int *d_sync = nullptr;        // [32 * max_batch + 16]: image order [max_batch] | per-image launch counters [max_batch] | K_A's
-                                  // 16 words | per-limb publication flags [max_batch][30] (see k_limb_connect); then: K_A's
-                                  // grid-wide ticket; zeroed ONCE here, re-armed by the kernels themselves (no memset node)
+    int *d_sync = nullptr;        // SyncWords::words(max_batch) ints, carved by SyncWords (below) and by nothing else; zeroed ONCE
+                                  // at create, re-armed by the kernels themselves (no memset node)
     int mode = 0;                 // pp_debug_set_mode
     void *d_maps = nullptr;       // [max_batch][48][plane stride] flip-averaged maps of shapes that do not fit LDS (k_flip_average_maps);
     size_t d_maps_bytes = 0;      // allocated at create only when an fp32 max_h x max_w map would not fit, or by pp_set_map_residency
@@ -123,28 +122,58 @@ int check_shape_resident(const pp_ctx *c, int batch, int dtype, int h, int w, bo
     return PP_OK;
 }
 
-// pp_process_batch for a map that stays in HBM: three launches -- the flip-average pre-pass, then K_A and K_B reading its
-// workspace.  Same workspaces, flags and ctx->mode meanings as the LDS form; the image sorter has LDS of its own here.
-int process_batch_hbm(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, int h, int w, int flip, int min_img_size,
-                      const int *min_img_size_dev, pp_record *rec, hipStream_t st) {
-    int *order = ctx->d_sync, *arrive = ctx->d_sync + ctx->max_batch, *arrive_all = ctx->d_sync + 2 * ctx->max_batch;
-    const bool sorted = ctx->mode == 0;
-    PP_HIP(ctx, pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st));
-    PP_HIP(ctx, pp::launch_heat_peaks_hbm(ctx->d_maps, dtype, batch, h, w, 1, 0, 0.1f, ctx->maxp, ctx->d_peaks, ctx->d_counts,
-                                          ctx->d_status, sorted ? order : nullptr, sorted ? arrive_all : nullptr, st));
-    PP_HIP(ctx, pp::launch_limb_connect_hbm(ctx->d_maps, dtype, batch, h, w, ctx->maxp, ctx->cap, min_img_size, min_img_size_dev,
-                                            ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux, ctx->d_conn_counts,
-                                            ctx->d_status, sorted ? order : nullptr, ctx->mode == 1 ? nullptr : arrive,
-                                            reinterpret_cast<unsigned *>(ctx->d_sync + 2 * ctx->max_batch + 16), rec, st));
-    if (ctx->mode == 1)
-        PP_HIP(ctx, pp::launch_assemble_wave(batch, ctx->maxp, ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux,
-                                             ctx->d_conn_counts, ctx->d_status, rec, st));
-    ctx->last_stream = st;
-    ctx->last_batch = batch;
-    ctx->last_peaks = ctx->d_peaks;
-    ctx->last_counts = ctx->d_counts;
-    return PP_OK;
-}
+// d_sync: [B] order | [B] arrive | 16 words, K_A's ticket first | [30 * B] ready (B = max_batch), carved here and nowhere else.
+// order: the images sorted by matching load (K_A's last workgroup writes it, K_B dispatches by it); arrive / ready: per-image
+// launch counters and per-limb publication flags (see k_limb_connect); arrive_all: K_A's grid-wide ticket.
+struct SyncWords {
+    int *order, *arrive, *arrive_all;
+    unsigned *ready;
+    static size_t words(int B) { return 2 * (size_t)B + 16 + PP_NUM_LIMB * (size_t)B; }
+    SyncWords(int *d_sync, int B)
+        : order(d_sync), arrive(d_sync + B), arrive_all(d_sync + 2 * B), ready(reinterpret_cast<unsigned *>(d_sync + 2 * B + 16)) {}
+};
+
+// The launches of one C++-rule entry point, for either residency (hbm: check_shape_resident's decision): K_A / K_B read the
+// caller's network output, or the context's workspace once fill_map has put the flip-averaged planes there.  sorted: K_A's last
+// workgroup orders the images by load for K_B (always possible in the HBM form, in the LDS form when the sorter's ints fit).
+struct Chain {
+    pp_ctx *ctx;
+    int batch;
+    hipStream_t st;
+    pp::MapSource src;
+    SyncWords sw;
+    bool sorted;
+    Chain(pp_ctx *c, bool hbm, int batch, const void *net, int dtype, int h, int w, int flip, hipStream_t st)
+        : ctx(c), batch(batch), st(st), src{hbm, hbm ? c->d_maps : net, dtype, h, w, flip ? 2 : 1, flip,
+                                            hbm ? pp::map_plane_stride(dtype == PP_F16 ? 2 : 4, h, w) : 0},
+          sw(c->d_sync, c->max_batch), sorted(c->mode == 0 && (hbm || pp::heat_peaks_sorts(dtype, batch, h, w, c->maxp))) {}
+    hipError_t fill_map(const void *net) const {   // the pre-pass of an HBM-resident map
+        if (!src.hbm) return hipSuccess;
+        return pp::launch_flip_average_maps(net, src.dtype, batch, src.n_samples, src.h, src.w, src.flip, ctx->d_maps, st);
+    }
+    hipError_t heat_peaks(int refine, int nms_mode, float thr, float4 *peaks, int *counts, bool sort) const {
+        return pp::launch_heat_peaks(src, batch, refine, nms_mode, thr, ctx->maxp, peaks, counts, ctx->d_status,
+                                     sort ? sw.order : nullptr, sort ? sw.arrive_all : nullptr, st);
+    }
+    // fused: workgroup 30 of each image assembles it into rec while its limbs are matched; otherwise assemble_wave follows
+    hipError_t limb_connect(int min_img_size, const int *min_img_size_dev, bool fused, pp_record *rec) const {
+        return pp::launch_limb_connect(src, batch, ctx->maxp, ctx->cap, min_img_size, min_img_size_dev, ctx->d_peaks, ctx->d_counts,
+                                       ctx->d_conns, ctx->d_conn_aux, ctx->d_conn_counts, ctx->d_status, sorted ? sw.order : nullptr,
+                                       fused ? sw.arrive : nullptr, sw.ready, rec, st);
+    }
+    hipError_t assemble_wave(pp_record *rec) const {
+        return pp::launch_assemble_wave(batch, ctx->maxp, ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux,
+                                        ctx->d_conn_counts, ctx->d_status, rec, st);
+    }
+};
+
+struct EventPair {   // the two events of a timing entry point, released on every return path
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
 
 }  // namespace
 
@@ -196,8 +225,8 @@ int pp_create(pp_ctx **out, int device, int max_batch, int max_h, int max_w, int
     if (e == hipSuccess) e = hipMalloc(&c->d_conns, B * PP_NUM_LIMB * c->maxp * sizeof(float4));
     if (e == hipSuccess) e = hipMalloc(&c->d_conn_counts, B * PP_NUM_LIMB * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&c->d_conn_aux, B * PP_NUM_LIMB * c->maxp * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc(&c->d_sync, (2 * B + 16 + PP_NUM_LIMB * B) * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(c->d_sync, 0, (2 * B + 16 + PP_NUM_LIMB * B) * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&c->d_sync, SyncWords::words(max_batch) * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(c->d_sync, 0, SyncWords::words(max_batch) * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&c->d_conns_py, B * PP_NUM_LIMB * c->maxp * 32);
     if (e == hipSuccess) e = hipMalloc(&c->d_persons, 128 * 40 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&c->d_npersons, sizeof(int));
@@ -268,18 +297,12 @@ int pp_nms_batch_ex(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, 
     int rc = check_shape_resident(ctx, batch, dtype, h, w, &hbm);
     if (rc != PP_OK) return rc;
     if (!net_out_dev || nms_mode < 0 || nms_mode > 1 || refine_mode < 0 || refine_mode > 3) return PP_ERR_BAD_ARG;
-    const int refine = refine_mode;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float4 *pk = peaks_dev ? reinterpret_cast<float4 *>(peaks_dev) : ctx->d_peaks;
     int *cn = counts_dev ? counts_dev : ctx->d_counts;
-    if (hbm) {
-        PP_HIP(ctx, pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st));
-        PP_HIP(ctx, pp::launch_heat_peaks_hbm(ctx->d_maps, dtype, batch, h, w, refine, nms_mode, threshold, ctx->maxp, pk, cn,
-                                              ctx->d_status, nullptr, nullptr, st));
-    } else {
-        PP_HIP(ctx, pp::launch_heat_peaks(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, refine, nms_mode, threshold,
-                                          ctx->maxp, pk, cn, ctx->d_status, nullptr, nullptr, st));
-    }
+    const Chain ch(ctx, hbm, batch, net_out_dev, dtype, h, w, flip, st);
+    PP_HIP(ctx, ch.fill_map(net_out_dev));
+    PP_HIP(ctx, ch.heat_peaks(refine_mode, nms_mode, threshold, pk, cn, false));   // no order / arrive_all
     ctx->last_stream = st;
     ctx->last_batch = batch;
     ctx->last_peaks = pk;
@@ -295,23 +318,14 @@ int pp_process_batch(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype,
     if (!net_out_dev) return PP_ERR_BAD_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     pp_record *rec = records_dev ? records_dev : ctx->d_records;
-    const int ns = flip ? 2 : 1;
-    if (hbm) return process_batch_hbm(ctx, batch, net_out_dev, dtype, h, w, flip, min_img_size, min_img_size_dev, rec, st);
-    // two launches: K_A (peaks; its last workgroup orders the images by load), K_B (limb scoring + matching; the last limb
-    // workgroup of each image assembles it).  ctx->mode: 0 as described, 1 = K_B and the assembly as separate launches,
-    // 2 = fused without the load ordering (A/B measurements, pp_debug_set_mode).
-    int *order = ctx->d_sync, *arrive = ctx->d_sync + ctx->max_batch, *arrive_all = ctx->d_sync + 2 * ctx->max_batch;
-    const bool sorted = ctx->mode == 0 && pp::heat_peaks_sorts(dtype, batch, h, w, ctx->maxp);
-    PP_HIP(ctx, pp::launch_heat_peaks(net_out_dev, dtype, batch, ns, h, w, flip, 1, 0, 0.1f, ctx->maxp, ctx->d_peaks,
-                                      ctx->d_counts, ctx->d_status, sorted ? order : nullptr, sorted ? arrive_all : nullptr, st));
-    PP_HIP(ctx, pp::launch_limb_connect(net_out_dev, dtype, batch, ns, h, w, flip, ctx->maxp, ctx->cap, min_img_size,
-                                        min_img_size_dev, ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux,
-                                        ctx->d_conn_counts, ctx->d_status, sorted ? order : nullptr,
-                                        ctx->mode == 1 ? nullptr : arrive,
-                                        reinterpret_cast<unsigned *>(ctx->d_sync + 2 * ctx->max_batch + 16), rec, st));
-    if (ctx->mode == 1)
-        PP_HIP(ctx, pp::launch_assemble_wave(batch, ctx->maxp, ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux,
-                                             ctx->d_conn_counts, ctx->d_status, rec, st));
+    // two launches (after the pre-pass of a map that stays in HBM): K_A (peaks; its last workgroup orders the images by load),
+    // K_B (limb scoring + matching; workgroup 30 of each image assembles it).  ctx->mode: 0 as described, 1 = K_B and the assembly
+    // as separate launches, 2 = fused without the load ordering (A/B measurements, pp_debug_set_mode).
+    const Chain ch(ctx, hbm, batch, net_out_dev, dtype, h, w, flip, st);
+    PP_HIP(ctx, ch.fill_map(net_out_dev));
+    PP_HIP(ctx, ch.heat_peaks(1, 0, 0.1f, ctx->d_peaks, ctx->d_counts, ch.sorted));
+    PP_HIP(ctx, ch.limb_connect(min_img_size, min_img_size_dev, ctx->mode != 1, rec));
+    if (ctx->mode == 1) PP_HIP(ctx, ch.assemble_wave(rec));
     ctx->last_stream = st;
     ctx->last_batch = batch;
     ctx->last_peaks = ctx->d_peaks;
@@ -331,7 +345,7 @@ int pp_process_batch_py(pp_ctx *ctx, int batch, const void *net_out_dev, int dty
     hipStream_t st = static_cast<hipStream_t>(stream);
     pp_record *rec = records_dev ? records_dev : ctx->d_records;
     const int ns = flip ? 2 : 1;
-    PP_HIP(ctx, pp::launch_heat_peaks(net_out_dev, dtype, batch, ns, h, w, flip, 1, 0, 0.1f, ctx->maxp, ctx->d_peaks,
+    PP_HIP(ctx, pp::launch_heat_peaks({false, net_out_dev, dtype, h, w, ns, flip, 0}, batch, 1, 0, 0.1f, ctx->maxp, ctx->d_peaks,
                                       ctx->d_counts, ctx->d_status, nullptr, nullptr, st));
     PP_HIP(ctx, pp::launch_limb_connect_py(net_out_dev, dtype, batch, ns, h, w, flip, ctx->maxp, ctx->cap, img_height,
                                            img_height_dev, ctx->d_peaks, ctx->d_counts, ctx->d_conns_py, ctx->d_conn_counts,
@@ -352,53 +366,34 @@ int pp_time_kernels(pp_ctx *ctx, int batch, const void *net_out_dev, int dtype, 
     if (rc != PP_OK) return rc;
     if (!net_out_dev || !ms_out || iters <= 0) return PP_ERR_BAD_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int ns = flip ? 2 : 1;
-    int *order = ctx->d_sync, *arrive = ctx->d_sync + ctx->max_batch, *arrive_all = ctx->d_sync + 2 * ctx->max_batch;
-    const bool sorted = ctx->mode == 0 && (hbm || pp::heat_peaks_sorts(dtype, batch, h, w, ctx->maxp));
-    unsigned *ready = reinterpret_cast<unsigned *>(ctx->d_sync + 2 * ctx->max_batch + 16);
-    hipEvent_t e0, e1;
-    PP_HIP(ctx, hipEventCreate(&e0));
-    PP_HIP(ctx, hipEventCreate(&e1));
-    // one untimed pass so that every kernel's inputs exist
+    EventPair ev;
+    PP_HIP(ctx, hipEventCreate(&ev.e0));
+    PP_HIP(ctx, hipEventCreate(&ev.e1));
+    // one untimed pass so that every kernel's inputs exist -- the workspace of an HBM-resident map included, which K_A and K_B
+    // are then timed on
     rc = pp_process_batch(ctx, batch, net_out_dev, dtype, h, w, flip, min_img_size, nullptr, nullptr, st);
     if (rc != PP_OK) return rc;
+    const Chain ch(ctx, hbm, batch, net_out_dev, dtype, h, w, flip, st);
     for (int k = 0; k < 4; k++) {
-        PP_HIP(ctx, hipEventRecord(e0, st));
+        PP_HIP(ctx, hipEventRecord(ev.e0, st));
         for (int i = 0; i < iters; i++) {
-            if (hbm && k == 0) {  // maps in HBM: the _hbm instances on the workspace the untimed pass filled
-                PP_HIP(ctx, pp::launch_heat_peaks_hbm(ctx->d_maps, dtype, batch, h, w, 1, 0, 0.1f, ctx->maxp, ctx->d_peaks,
-                                                      ctx->d_counts, ctx->d_status, sorted ? order : nullptr,
-                                                      sorted ? arrive_all : nullptr, st));
-            } else if (hbm && k == 1) {
-                PP_HIP(ctx, pp::launch_limb_connect_hbm(ctx->d_maps, dtype, batch, h, w, ctx->maxp, ctx->cap, min_img_size, nullptr,
-                                                        ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_aux, ctx->d_conn_counts,
-                                                        ctx->d_status, sorted ? order : nullptr, arrive, ready, ctx->d_records, st));
-            } else if (k == 3) {  // the whole chain, back to back, as pp_process_batch enqueues it
+            if (k == 0) {
+                PP_HIP(ctx, ch.heat_peaks(1, 0, 0.1f, ctx->d_peaks, ctx->d_counts, ch.sorted));
+            } else if (k == 1) {  // limb scoring + matching with the assembly tail (the product's second launch), whatever the mode
+                PP_HIP(ctx, ch.limb_connect(min_img_size, nullptr, true, ctx->d_records));
+            } else if (k == 2) {  // the assembly alone, one wave per image, as its own launch (diagnostic)
+                PP_HIP(ctx, ch.assemble_wave(ctx->d_records));
+            } else {  // the whole chain, back to back, as pp_process_batch enqueues it
                 rc = pp_process_batch(ctx, batch, net_out_dev, dtype, h, w, flip, min_img_size, nullptr, nullptr, st);
                 if (rc != PP_OK) return rc;
-            } else if (k == 0) {
-                PP_HIP(ctx, pp::launch_heat_peaks(net_out_dev, dtype, batch, ns, h, w, flip, 1, 0, 0.1f, ctx->maxp,
-                                                  ctx->d_peaks, ctx->d_counts, ctx->d_status, sorted ? order : nullptr,
-                                                  sorted ? arrive_all : nullptr, st));
-            } else if (k == 1) {  // limb scoring + matching with the assembly tail (the product's second launch)
-                PP_HIP(ctx, pp::launch_limb_connect(net_out_dev, dtype, batch, ns, h, w, flip, ctx->maxp, ctx->cap,
-                                                    min_img_size, nullptr, ctx->d_peaks, ctx->d_counts, ctx->d_conns,
-                                                    ctx->d_conn_aux, ctx->d_conn_counts, ctx->d_status,
-                                                    sorted ? order : nullptr, arrive,
-                                                    reinterpret_cast<unsigned *>(ctx->d_sync + 2 * ctx->max_batch + 16), ctx->d_records, st));
-            } else {  // the assembly alone, one wave per image, as its own launch (diagnostic)
-                PP_HIP(ctx, pp::launch_assemble_wave(batch, ctx->maxp, ctx->d_peaks, ctx->d_counts, ctx->d_conns,
-                                                     ctx->d_conn_aux, ctx->d_conn_counts, ctx->d_status, ctx->d_records, st));
             }
         }
-        PP_HIP(ctx, hipEventRecord(e1, st));
-        PP_HIP(ctx, hipEventSynchronize(e1));
+        PP_HIP(ctx, hipEventRecord(ev.e1, st));
+        PP_HIP(ctx, hipEventSynchronize(ev.e1));
         float ms = 0.f;
-        PP_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+        PP_HIP(ctx, hipEventElapsedTime(&ms, ev.e0, ev.e1));
         ms_out[k] = ms / (float)iters;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return PP_OK;
 }
 
@@ -411,20 +406,17 @@ int pp_time_map_prepass(pp_ctx *ctx, int batch, const void *net_out_dev, int dty
     *ms_out = 0.f;
     if (!hbm) return PP_OK;   // the map is staged in LDS: there is no pre-pass
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair ev;
+    PP_HIP(ctx, hipEventCreate(&ev.e0));
+    PP_HIP(ctx, hipEventCreate(&ev.e1));
+    PP_HIP(ctx, pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st));  // untimed
+    PP_HIP(ctx, hipEventRecord(ev.e0, st));
+    for (int i = 0; i < iters; i++)
+        PP_HIP(ctx, pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st));
+    PP_HIP(ctx, hipEventRecord(ev.e1, st));
+    PP_HIP(ctx, hipEventSynchronize(ev.e1));
     float ms = 0.f;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st);  // untimed
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    for (int i = 0; i < iters && e == hipSuccess; i++)
-        e = pp::launch_flip_average_maps(net_out_dev, dtype, batch, flip ? 2 : 1, h, w, flip, ctx->d_maps, st);
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);   // on every path, failures included
-    if (e1) (void)hipEventDestroy(e1);
-    PP_HIP(ctx, e);
+    PP_HIP(ctx, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     *ms_out = ms / (float)iters;
     return PP_OK;
 }
@@ -563,7 +555,7 @@ int pp_process_paf_host(pp_ctx *ctx, int p1, int p2, int p3, const float *peaks,
     PP_HIP(ctx, hipMemcpyAsync(ctx->d_counts, counts, sizeof(counts), hipMemcpyHostToDevice, st));
     PP_HIP(ctx, pp::launch_limb_connect_hwc(ctx->d_paf, f1, f2, f3, maxp, ctx->cap, min_img_size, ctx->d_peaks,
                                             ctx->d_counts, ctx->d_conns, ctx->d_conn_counts, ctx->d_status, st));
-    PP_HIP(ctx, pp::launch_assemble(1, maxp, 1, ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_counts,
+    PP_HIP(ctx, pp::launch_assemble(1, maxp, ctx->d_peaks, ctx->d_counts, ctx->d_conns, ctx->d_conn_counts,
                                     ctx->d_status, PP_NUM_PART, ctx->d_records, st));  // no peak kernel ran: limb words only
     PP_HIP(ctx, hipMemcpyAsync(&ctx->h_record, ctx->d_records, sizeof(pp_record), hipMemcpyDeviceToHost, st));
     PP_HIP(ctx, hipStreamSynchronize(st));

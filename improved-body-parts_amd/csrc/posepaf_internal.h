@@ -30,20 +30,17 @@ size_t lds_bytes_limb(int elem, int h, int w, int maxp, int cap);
 size_t lds_bytes_limb_hwc(int maxp, int cap);
 size_t lds_bytes_assemble(int maxp);
 
-// order / arrive_all (both or neither): K_A's last workgroup writes the images sorted by matching load into order[batch]
-hipError_t launch_heat_peaks(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, int refine,
-                             int nms_mode, float thr, int maxp, float4 *peaks, int *counts, unsigned *status, int *order,
-                             int *arrive_all, hipStream_t stream);
-bool heat_peaks_sorts(int dtype, int batch, int h, int w, int maxp);
-// arrive != NULL: fused form, workgroup 30 of each image assembles it into records WHILE its limbs are matched (arrive[batch]:
-// per-image launch counters, ready[batch][30]: per-limb publication flags; both zeroed once at create and owned by the kernel);
-// arrive == NULL: connections only (launch_assemble_wave follows).  order may be NULL.
-hipError_t launch_limb_connect(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, int maxp,
-                               int cap, int min_img_size, const int *min_img_size_dev, const float4 *peaks,
-                               const int *counts, float4 *conns, float4 *aux, int *conn_counts, unsigned *status,
-                               const int *order, int *arrive, unsigned *ready, pp_record *records, hipStream_t stream);
-// Maps larger than LDS: launch_flip_average_maps writes the 48 used channels, flip-averaged, into
-// ws[batch][48][map_plane_stride] (element type = dtype); the _hbm launchers are K_A / K_B reading that workspace instead of LDS.
+// Where K_A / K_B read the feature map of shape (h, w) and element type dtype.  !hbm: ptr is the caller's network output
+// (batch, n_samples, 50, h, w), which the kernels flip-average into LDS themselves.  hbm: ptr is the workspace
+// ws[batch][48][ws_stride] that launch_flip_average_maps filled from it (maps larger than LDS); the
+// launchers then run the _hbm instances, which read it in place.
+struct MapSource {
+    bool hbm;
+    const void *ptr;
+    int dtype, h, w;
+    int n_samples, flip;   // of the network output (the kernels read them only when !hbm)
+    size_t ws_stride;      // hbm only: elements per plane (map_plane_stride)
+};
 constexpr size_t kMaxHbmPixels = (size_t)650 * 950;   // the reference's own cap on this path (utils/parse_skeletons.py:46-49), / 4
 size_t lds_bytes_heat_hbm(int h, int w, int maxp, int batch);
 size_t lds_bytes_limb_hbm(int maxp, int cap);
@@ -51,21 +48,27 @@ size_t map_plane_stride(int elem, int h, int w);    // elements: h*w rounded up 
 size_t map_workspace_bytes(int batch, int h, int w);  // batch * 48 planes of fp32 + 16 bytes of slack
 hipError_t launch_flip_average_maps(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, void *ws,
                                     hipStream_t stream);
-hipError_t launch_heat_peaks_hbm(const void *ws, int dtype, int batch, int h, int w, int refine, int nms_mode, float thr, int maxp,
-                                 float4 *peaks, int *counts, unsigned *status, int *order, int *arrive_all, hipStream_t stream);
-hipError_t launch_limb_connect_hbm(const void *ws, int dtype, int batch, int h, int w, int maxp, int cap, int min_img_size,
-                                   const int *min_img_size_dev, const float4 *peaks, const int *counts, float4 *conns, float4 *aux,
-                                   int *conn_counts, unsigned *status, const int *order, int *arrive, unsigned *ready,
-                                   pp_record *records, hipStream_t stream);
+// order / arrive_all (both or neither): K_A's last workgroup writes the images sorted by matching load into order[batch]
+hipError_t launch_heat_peaks(const MapSource &src, int batch, int refine, int nms_mode, float thr, int maxp, float4 *peaks,
+                             int *counts, unsigned *status, int *order, int *arrive_all, hipStream_t stream);
+bool heat_peaks_sorts(int dtype, int batch, int h, int w, int maxp);
+// arrive != NULL: fused form, workgroup 30 of each image assembles it into records WHILE its limbs are matched (arrive[batch]:
+// per-image launch counters, ready[batch][30]: per-limb publication flags; both zeroed once at create and owned by the kernel);
+// arrive == NULL: connections only (launch_assemble_wave follows).  order may be NULL.
+hipError_t launch_limb_connect(const MapSource &src, int batch, int maxp, int cap, int min_img_size, const int *min_img_size_dev,
+                               const float4 *peaks, const int *counts, float4 *conns, float4 *aux, int *conn_counts,
+                               unsigned *status, const int *order, int *arrive, unsigned *ready, pp_record *records,
+                               hipStream_t stream);
 hipError_t launch_assemble_wave(int batch, int maxp, const float4 *peaks, const int *counts, const float4 *conns,
                                 const float4 *aux, const int *conn_counts, const unsigned *status, pp_record *records,
                                 hipStream_t stream);
 hipError_t launch_limb_connect_hwc(const float *paf, int H, int W, int C, int maxp, int cap, int min_img_size,
                                    const float4 *peaks, const int *counts, float4 *conns, int *conn_counts,
                                    unsigned *status, hipStream_t stream);
-hipError_t launch_assemble(int batch, int maxp, int explicit_ids, const float4 *peaks, const int *counts,
-                           const float4 *conns, const int *conn_counts, const unsigned *status, int flag_first,
-                           pp_record *records, hipStream_t stream);
+// the drop-in process_paf's assembly, in the reference's order; peak ids are the .w bits of the peaks
+hipError_t launch_assemble(int batch, int maxp, const float4 *peaks, const int *counts, const float4 *conns,
+                           const int *conn_counts, const unsigned *status, int flag_first, pp_record *records,
+                           hipStream_t stream);
 
 // The Python-twin launchers take the context's test configuration (cfg; NULL = the INI defaults).  Each kernel's general
 // instance is launched only when a value IT reads differs from the default; otherwise the instance with the literals runs.

@@ -13,8 +13,9 @@
 //        of the limb through a per-limb flag;
 //        workgroup 30 of an image: ONE wave that assembles the image (A7) WHILE its limbs are matched -- it
 //        consumes limb 0, 1, ... as each is published, prunes, and writes the fixed-size result record
-//   (k_assemble_wave / k_assemble: the assembly as its own launch -- diagnostics, the drop-in process_paf and the
-//   Python-twin path; k_accumulate_scales + k_fullres_peaks + ...: the original path at image resolution.)
+//   (k_assemble_wave: the same assembly as its own launch, for diagnostics.  k_limb_connect_hwc + k_assemble: the drop-in
+//   process_paf on the caller's peaks and up-sampled map, connection by connection in the reference's order.  k_*_py: the
+//   Python-twin path.  k_accumulate_scales + k_fullres_peaks + ...: the original path at image resolution.)
 //
 // No MFMA anywhere: this is gather/compare/reduce work bounded by HBM.
 // Floating point: every expression mirrors the reference's operation ORDER and rounding (x86-64 g++ without
@@ -984,7 +985,7 @@ __device__ int connect_limb(const Sampler &smp, const LimbLds &L, int nA, int nB
 // ------------------------------------------------------------------------------------------------ K_C, wave form
 // pafprocess.cpp:132-285 for ONE image by ONE wave -- the form the batched path uses, either as the tail of K_B (the last
 // limb workgroup of an image to finish runs it: k_limb_connect) or as a kernel of its own (k_assemble_wave: timing,
-// diagnostics).  Same results as k_assemble above, different mechanics:
+// diagnostics).  Same results as the drop-in path's k_assemble below, different mechanics:
 //   * STABLE SLOTS.  A skeleton is born into the next free slot and never moves; `skeletons.erase` (:228) only marks the
 //     slot dead.  The reference's vector order is the birth order of the live skeletons, so "first match" / "second match"
 //     of the scan (:143-150) are the lowest / second-lowest matching slot and the output order is slot order.  No row shifts.
@@ -1735,7 +1736,11 @@ __global__ __launch_bounds__(kThreads) void k_limb_connect_hwc(const float *__re
     connect_limb(smp, L, nA, nB, cap, maxp, min_img_size, conns + (size_t)limb * maxp, cc, status + PP_NUM_PART + limb);
 }
 
-// ------------------------------------------------------------------------------------------------ K_C
+// ------------------------------------------------------------------------------------------------ drop-in assembly
+// k_assemble is the assembly of the drop-in process_paf and of nothing else: the caller's connections, one by one, in the
+// reference's order (pafprocess.cpp:133-275), then the prune and the record.  Peak ids are the caller's (the .w bits of each
+// peak: the row's position in the input, :34), which need not be the position in the part-bucketed line -- so every connection
+// scans the live skeletons as the reference does.  (The product path's assembly is assemble_image_wave above.)
 // One wave per image.  Skeleton table in LDS: entry [s][k], k in [0,18) = {peak id, limb score},
 // k = 18 = {-, total score}, k = 19 = {part count, longest limb} (pafprocess.h:36-45, pafprocess.cpp:11-12).
 // The scan over live skeletons (pafprocess.cpp:143-150) is done by the 64 lanes with ballots; the matched
@@ -1744,10 +1749,10 @@ constexpr int kMaxSkel = 256;
 constexpr int kSkelStride = 21;  // 20 entries, odd stride: the per-lane column reads of the scan are conflict-free
 
 __host__ __device__ inline size_t assemble_lds_bytes(int maxp) {
-    return (size_t)kMaxSkel * kSkelStride * 8 + (size_t)PP_NUM_PART * maxp * 16 + (size_t)PP_NUM_LIMB * maxp * 16 + 16 * (size_t)maxp;
+    return (size_t)kMaxSkel * kSkelStride * 8 + (size_t)PP_NUM_PART * maxp * 16 + (size_t)PP_NUM_LIMB * maxp * 16;
 }
 
-__global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, const float4 *__restrict__ peaks,
+__global__ __launch_bounds__(64) void k_assemble(int maxp, const float4 *__restrict__ peaks,
                                                  const int *__restrict__ counts, const float4 *__restrict__ conns,
                                                  const int *__restrict__ conn_counts, const unsigned *__restrict__ status,
                                                  int flag_first, pp_record *__restrict__ records) {
@@ -1761,19 +1766,12 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
     float *line_s = reinterpret_cast<float *>(line_y + ntab);
     int *ids = reinterpret_cast<int *>(line_s + ntab);                      // [18][maxp] peak id of (part, rank)
     float4 *s_conn = reinterpret_cast<float4 *>(ids + ntab);                // all connections, limb-major, compact
-    int *s_own1 = reinterpret_cast<int *>(s_conn + PP_NUM_LIMB * maxp);     // [maxp] skeleton holding peak r at part 1 / 2
-    int *s_own2 = s_own1 + maxp;
-    int *s_cb1 = s_own2 + maxp;                                             // [maxp] connection using peak r as end point 1 / 2
-    int *s_cb2 = s_cb1 + maxp;
     __shared__ int s_off[PP_NUM_PART + 1];
-    __shared__ int s_cnt[PP_NUM_PART];
     __shared__ int s_coff[PP_NUM_LIMB + 1];
-    __shared__ int s_conf[64];  // per connection of the current limb: shares a skeleton with another connection
 
     const int *cnt_g = counts + img * PP_NUM_PART;
     const float4 *pk_g = peaks + (size_t)img * PP_NUM_PART * maxp;
     long long *stamps = d_stamps;
-    long long seq_cycles = 0, seq_limbs = 0, odd_merges = 0;
     stamp(stamps, img, 0);
     {  // bucket offsets: one count per lane, wave prefix sums (no serial chain of global loads)
         int c = lane < PP_NUM_PART ? cnt_g[lane] : 0;
@@ -1790,7 +1788,6 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
             }
         }
         if (lane < PP_NUM_PART) {
-            s_cnt[lane] = c;
             s_off[lane] = inc - c;
             if (lane == PP_NUM_PART - 1) s_off[PP_NUM_PART] = inc;
         }
@@ -1810,7 +1807,7 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
             line_x[i] = (int)p.x;
             line_y[i] = (int)p.y;
             line_s[i] = p.z;
-            ids[part * maxp + r] = explicit_ids ? __float_as_int(p.w) : i;  // :34 ids follow input order
+            ids[part * maxp + r] = __float_as_int(p.w);  // :34 ids follow input order
         }
     }
     __syncthreads();
@@ -1826,20 +1823,10 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
         }
     }
     __syncthreads();
-
-    for (int i = lane; i < 4 * maxp; i += 64) s_own1[i] = 0;  // own1, own2, cb1, cb2 (contiguous); tag 0 = never valid
-    __syncthreads();
     stamp(stamps, img, 1);
     int nskel = 0;  // uniform
     unsigned st = 0;
-    // The connections of ONE limb type have pairwise different end points, so they touch pairwise different skeletons
-    // unless (a) a skeleton holds the part-1 peak of one connection and the part-2 peak of another, (b) two skeletons
-    // hold the same peak, or (c) a connection joins two skeletons (possible merge + erase).  When none of that
-    // happens -- checked exactly, per limb -- the sequential scan of pafprocess.cpp:138-275 gives the same result in
-    // any order, and the limb's connections are applied in parallel (one lane each): owner tables peak -> skeleton
-    // replace the O(#skeletons) scan.  Otherwise the limb is processed connection by connection as the reference does.
-    auto sequential_conn = [&](int ci, int part1, int part2) -> int {  // returns the erased skeleton's index or -1
-        int erased = -1;
+    auto sequential_conn = [&](int ci, int part1, int part2) {  // one connection, pafprocess.cpp:138-275
         const float4 cn = s_conn[ci];
         const int id1 = __float_as_int(cn.x), id2 = __float_as_int(cn.y);
         const float c_score = cn.z, c_len = cn.w;
@@ -1898,7 +1885,7 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
             const float a_f1 = isp ? f1[lane] : 0.0f, a_f2 = isp ? f2[lane] : 0.0f;
             const bool a1 = a_i1 > 0, a2 = a_i2 > 0;  // :200-201 id 0 counts as unassigned
             const bool is_member = __ballot(a1 && a2) != 0;
-            int merge = 0;
+            bool merge = false;
             if (!is_member) {
                 // :203-214 running minima "min = (min == 0) ? v : min(v, min)": a plain minimum unless a value is exactly 0
                 float min1, min2;
@@ -1927,9 +1914,7 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
                 const int min_len = (int)__fmul_rn(len1, 16.0f);
                 const float lim = __fmul_rn((min2 < min1 ? min2 : min1), 0.7f);  // :220
                 if (c_score >= lim || c_len < (float)min_len) {                   // :221 OR
-                    // a column where BOTH rows hold an id gets their sum + 1: an id no lookup table knows (see below)
-                    const bool odd = __ballot((lane == part1 || lane == part2) && a_i1 >= 0 && a_i2 >= 0) != 0;
-                    merge = odd ? 3 : 1;
+                    merge = true;   // :223-224 every column gets id1 + (id2 + 1), also where BOTH rows hold an id
                     const float tot = __fadd_rn(f1[18], __fadd_rn(f2[18], c_score));
                     const int cnt = i1[19] + i2[19];
                     if (isp) {
@@ -1960,7 +1945,6 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
                     __syncthreads();
                 }
                 nskel--;
-                erased = idx2 | ((merge & 2) << 15);
             }
             __syncthreads();
         } else if (num_found == 0) {  // :257-273
@@ -1982,152 +1966,13 @@ __global__ __launch_bounds__(64) void k_assemble(int maxp, int explicit_ids, con
             __syncthreads();
         }
         // num_found > 2: no action
-        return erased;
     };
     for (int limb = 0; limb < PP_NUM_LIMB; limb++) {
         const int part1 = d_limb_pairs[limb][0], part2 = d_limb_pairs[limb][1];
-        const int c0 = s_coff[limb], m = s_coff[limb + 1] - c0;
-        if (m == 0) continue;
-        if (explicit_ids || m > 64 || nskel + m > kMaxSkel) {  // plain reference order
-            for (int ci = c0; ci < c0 + m; ci++) sequential_conn(ci, part1, part2);
-            continue;
-        }
-        const int off1 = s_off[part1], off2 = s_off[part2], cnt1 = s_cnt[part1], cnt2 = s_cnt[part2];
-        // table entries carry the limb as a tag (tables zeroed once per launch), so nothing is re-initialised per limb
-        const int tag = (limb + 1) << 8;
-        int id1 = 0, id2 = 0;
-        float c_score = 0.0f, c_len = 0.0f;
-        if (lane < m) {
-            const float4 cn = s_conn[c0 + lane];
-            id1 = __float_as_int(cn.x);
-            id2 = __float_as_int(cn.y);
-            c_score = cn.z;
-            c_len = cn.w;
-            s_cb1[id1 - off1] = tag | lane;  // end points are distinct within a limb: no write conflicts
-            s_cb2[id2 - off2] = tag | lane;
-        }
-        s_conf[lane] = 0;
-        for (int sb = 0; sb < nskel; sb += 64) {  // owner tables: which skeleton holds peak r at part 1 / part 2
-            const int sidx = sb + lane;
-            if (sidx < nskel) {
-                const int r1 = sk_id[sidx * kSkelStride + part1] - off1, r2 = sk_id[sidx * kSkelStride + part2] - off2;
-                if (r1 >= 0 && r1 < cnt1) s_own1[r1] = tag | sidx;
-                if (r2 >= 0 && r2 < cnt2) s_own2[r2] = tag | sidx;
-            }
-        }
-        __syncthreads();
-        for (int sb = 0; sb < nskel; sb += 64) {  // skeleton lanes flag the connections that are not alone on a skeleton
-            const int sidx = sb + lane;
-            if (sidx < nskel) {
-                const int r1 = sk_id[sidx * kSkelStride + part1] - off1, r2 = sk_id[sidx * kSkelStride + part2] - off2;
-                int k1 = -1, k2 = -1;
-                bool multi1 = false, multi2 = false;
-                if (r1 >= 0 && r1 < cnt1) {
-                    multi1 = s_own1[r1] != (tag | sidx);  // (b): another skeleton wrote the same entry
-                    const int v = s_cb1[r1];
-                    if ((v & ~0xff) == tag) k1 = v & 0xff;
-                }
-                if (r2 >= 0 && r2 < cnt2) {
-                    multi2 = s_own2[r2] != (tag | sidx);
-                    const int v = s_cb2[r2];
-                    if ((v & ~0xff) == tag) k2 = v & 0xff;
-                }
-                const bool two = k1 >= 0 && k2 >= 0 && k1 != k2;  // (a): one skeleton, two different connections
-                if (k1 >= 0 && (multi1 || two)) s_conf[k1] = 1;
-                if (k2 >= 0 && (multi2 || two)) s_conf[k2] = 1;
-            }
-        }
-        __syncthreads();
-        int idx1 = -1;
-        bool conflict = false;
-        if (lane < m) {
-            int o1 = s_own1[id1 - off1], o2 = s_own2[id2 - off2];
-            o1 = (o1 & ~0xff) == tag ? (o1 & 0xff) : -1;
-            o2 = (o2 & ~0xff) == tag ? (o2 & 0xff) : -1;
-            conflict = s_conf[lane] != 0 || (o1 >= 0 && o2 >= 0 && o1 != o2);  // (c) two skeletons: possible merge
-            idx1 = o1 >= 0 ? o1 : o2;
-        }
-        unsigned long long confm = __ballot(conflict);
-        const float ps1 = (lane < m && id1 >= 0 && id1 < n_peaks) ? line_s[id1] : 0.0f;
-        const float ps2 = (lane < m && id2 >= 0 && id2 < n_peaks) ? line_s[id2] : 0.0f;
-        // ---- connections in order: maximal runs of independent ones in one step each, the others one by one
-        int pos = 0;
-        while (pos < m) {
-            const unsigned long long rest = confm >> pos;
-            int next = rest ? pos + __ffsll((long long)rest) - 1 : m;
-            next = next < m ? next : m;
-            if (next > pos) {
-                const bool mine = lane >= pos && lane < next;
-                const bool is_new = mine && idx1 < 0;
-                const unsigned long long mnew = __ballot(is_new);
-                if (mine && idx1 >= 0) {  // :152-180 on a skeleton no other connection of this limb touches
-                    int *i1 = sk_id + idx1 * kSkelStride;
-                    float *f1 = sk_sc + idx1 * kSkelStride;
-                    const float len1 = f1[19];
-                    const int min_len = (int)__fmul_rn(len1, 16.0f);
-                    const int cur_id = i1[part2];
-                    const float cur_sc = f1[part2];
-                    if (cur_id == -1 && (float)min_len > c_len) {
-                        i1[part2] = id2;
-                        f1[part2] = c_score;
-                        i1[19] += 1;
-                        f1[19] = len1 < c_len ? c_len : len1;
-                        f1[18] = __fadd_rn(f1[18], __fadd_rn(ps2, c_score));
-                    } else if ((cur_id != id2 && cur_sc <= c_score && (float)min_len > c_len) ||
-                               (cur_id == id2 && cur_sc <= c_score)) {
-                        i1[part2] = id2;
-                        f1[part2] = c_score;
-                        const float t = __fadd_rn(ps2, c_score);
-                        f1[18] = __fadd_rn(__fadd_rn(f1[18], -t), t);
-                        f1[19] = len1 < c_len ? c_len : len1;
-                    }
-                } else if (is_new) {  // :257-273 new skeleton; slots in connection order
-                    const int slot = nskel + __popcll(mnew & lanemask_lt());
-                    int *i1 = sk_id + slot * kSkelStride;
-                    float *f1 = sk_sc + slot * kSkelStride;
-#pragma unroll
-                    for (int k = 0; k < 20; k++) {
-                        i1[k] = -1;
-                        f1[k] = -1.0f;
-                    }
-                    i1[part1] = id1;
-                    f1[part1] = c_score;
-                    i1[part2] = id2;
-                    f1[part2] = c_score;
-                    i1[19] = 2;
-                    f1[19] = c_len;
-                    f1[18] = __fadd_rn(__fadd_rn(ps1, ps2), c_score);
-                }
-                nskel += __popcll(mnew);
-                __syncthreads();
-            }
-            if (next < m) {
-                const long long t0 = stamps ? (long long)clock64() : 0;
-                const int erased = sequential_conn(c0 + next, part1, part2);
-                if (erased >= 0) {
-                    if (idx1 > (erased & 0xffff)) idx1--;  // skeletons.erase shifted every later skeleton down one slot
-                    // a merge that ADDS two real ids in the part-1/part-2 column makes an id no table knows: from
-                    // here on every connection of this limb scans the skeletons as the reference does
-                    if (erased >> 16) {
-                        confm |= ~0ull << next;
-                        odd_merges++;
-                    }
-                }
-                if (stamps) {
-                    seq_cycles += (long long)clock64() - t0;
-                    seq_limbs++;
-                }
-            }
-            pos = next + 1;
-        }
+        for (int ci = s_coff[limb]; ci < s_coff[limb + 1]; ci++) sequential_conn(ci, part1, part2);
     }
     __syncthreads();
     stamp(stamps, img, 2);
-    if (stamps && lane == 0) {
-        stamps[(size_t)img * 8 + 4] = seq_limbs;
-        stamps[(size_t)img * 8 + 5] = seq_cycles;
-        stamps[(size_t)img * 8 + 6] = odd_merges;
-    }
 
     // ---- prune (:278-282) + records; order of survivors preserved
     pp_record *rec = records + img;
@@ -2971,18 +2816,30 @@ hipError_t init_kernel_attributes() {
     return hipSuccess;
 }
 
-hipError_t launch_heat_peaks(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, int refine,
-                             int nms_mode, float thr, int maxp, float4 *peaks, int *counts, unsigned *status, int *order,
-                             int *arrive_all, hipStream_t stream) {
+// The element-type switch of every launcher of a templated kernel, written once: f(e) with decltype(e) = __half or float.
+template <typename F>
+void for_dtype(int dtype, F &&f) {
+    if (dtype == PP_F16) f(__half());
+    else f(float());
+}
+
+hipError_t launch_heat_peaks(const MapSource &src, int batch, int refine, int nms_mode, float thr, int maxp, float4 *peaks,
+                             int *counts, unsigned *status, int *order, int *arrive_all, hipStream_t stream) {
     const dim3 grid(PP_NUM_PART, batch), block(kThreads);
-    const size_t lds = lds_bytes_heat(dtype == PP_F16 ? 2 : 4, h, w, maxp);
-    if ((size_t)batch * sizeof(int) > lds) order = nullptr;  // the sorter keeps one int per image in the map's LDS region
-    if (dtype == PP_F16)
-        hipLaunchKernelGGL(k_heat_peaks<__half>, grid, block, lds, stream, static_cast<const __half *>(net), n_samples, h,
-                           w, flip, refine, nms_mode, thr, maxp, peaks, counts, status, order, arrive_all);
-    else
-        hipLaunchKernelGGL(k_heat_peaks<float>, grid, block, lds, stream, static_cast<const float *>(net), n_samples, h, w,
-                           flip, refine, nms_mode, thr, maxp, peaks, counts, status, order, arrive_all);
+    const int h = src.h, w = src.w;
+    const size_t lds = src.hbm ? lds_bytes_heat_hbm(h, w, maxp, batch) : lds_bytes_heat(src.dtype == PP_F16 ? 2 : 4, h, w, maxp);
+    // LDS form: the sorter keeps one int per image in the map's LDS region (the _hbm instance has `batch` ints of its own)
+    if (!src.hbm && (size_t)batch * sizeof(int) > lds) order = nullptr;
+    for_dtype(src.dtype, [&](auto e) {
+        using T = decltype(e);
+        const T *map = static_cast<const T *>(src.ptr);
+        if (src.hbm)
+            hipLaunchKernelGGL(k_heat_peaks_hbm<T>, grid, block, lds, stream, map, src.ws_stride, h, w, refine, nms_mode, thr, maxp,
+                               peaks, counts, status, order, arrive_all);
+        else
+            hipLaunchKernelGGL(k_heat_peaks<T>, grid, block, lds, stream, map, src.n_samples, h, w, src.flip, refine, nms_mode, thr,
+                               maxp, peaks, counts, status, order, arrive_all);
+    });
     return hipGetLastError();
 }
 bool heat_peaks_sorts(int dtype, int batch, int h, int w, int maxp) {
@@ -2998,73 +2855,44 @@ int limb_threads() {
     }();
     return nt;
 }
+// the 256 / 512-thread switch, written once: the instance of a K_B kernel that limb_threads() selects
+template <typename K>
+K for_limb_threads(K k256, K k512) {
+    return limb_threads() == 512 ? k512 : k256;
+}
 
-hipError_t launch_limb_connect(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, int maxp,
-                               int cap, int min_img_size, const int *min_img_size_dev, const float4 *peaks,
-                               const int *counts, float4 *conns, float4 *aux, int *conn_counts, unsigned *status,
-                               const int *order, int *arrive, unsigned *ready, pp_record *records, hipStream_t stream) {
-    const int nt = limb_threads();
-    const dim3 grid(PP_NUM_LIMB + (arrive ? 1 : 0), batch), block(nt);   // fused form: workgroup 30 of an image assembles it
-    const size_t lds = lds_bytes_limb(dtype == PP_F16 ? 2 : 4, h, w, maxp, cap);  // >= the assembly tail's need
-#define PP_LAUNCH_LIMB(T, NT)                                                                                                   \
-    hipLaunchKernelGGL((k_limb_connect<T, NT>), grid, block, lds, stream, static_cast<const T *>(net), n_samples, h, w, flip, maxp, \
-                       cap, min_img_size, min_img_size_dev, peaks, counts, conns, aux, conn_counts, status, order, arrive, ready, records)
-    if (dtype == PP_F16) {
-        if (nt == 512) PP_LAUNCH_LIMB(__half, 512);
-        else PP_LAUNCH_LIMB(__half, 256);
-    } else {
-        if (nt == 512) PP_LAUNCH_LIMB(float, 512);
-        else PP_LAUNCH_LIMB(float, 256);
-    }
-#undef PP_LAUNCH_LIMB
+hipError_t launch_limb_connect(const MapSource &src, int batch, int maxp, int cap, int min_img_size, const int *min_img_size_dev,
+                               const float4 *peaks, const int *counts, float4 *conns, float4 *aux, int *conn_counts,
+                               unsigned *status, const int *order, int *arrive, unsigned *ready, pp_record *records,
+                               hipStream_t stream) {
+    const dim3 grid(PP_NUM_LIMB + (arrive ? 1 : 0), batch), block(limb_threads());   // fused form: workgroup 30 of an image assembles it
+    const int h = src.h, w = src.w;
+    const size_t lds = src.hbm ? lds_bytes_limb_hbm(maxp, cap) : lds_bytes_limb(src.dtype == PP_F16 ? 2 : 4, h, w, maxp, cap);  // >= the tail's need
+    for_dtype(src.dtype, [&](auto e) {
+        using T = decltype(e);
+        const T *map = static_cast<const T *>(src.ptr);
+        if (src.hbm)
+            hipLaunchKernelGGL(for_limb_threads(k_limb_connect_hbm<T, 256>, k_limb_connect_hbm<T, 512>), grid, block, lds, stream, map,
+                               src.ws_stride, h, w, maxp, cap, min_img_size, min_img_size_dev, peaks, counts, conns, aux, conn_counts,
+                               status, order, arrive, ready, records);
+        else
+            hipLaunchKernelGGL(for_limb_threads(k_limb_connect<T, 256>, k_limb_connect<T, 512>), grid, block, lds, stream, map,
+                               src.n_samples, h, w, src.flip, maxp, cap, min_img_size, min_img_size_dev, peaks, counts, conns, aux,
+                               conn_counts, status, order, arrive, ready, records);
+    });
     return hipGetLastError();
 }
 
-// ---- maps larger than LDS: pre-pass + the _hbm instances (ws: map_workspace_bytes, planes of map_plane_stride elements)
+// ---- maps larger than LDS: the pre-pass that fills the MapSource workspace (ws: map_workspace_bytes, planes of map_plane_stride
+// elements)
 hipError_t launch_flip_average_maps(const void *net, int dtype, int batch, int n_samples, int h, int w, int flip, void *ws,
                                     hipStream_t stream) {
     const dim3 grid(kWsChannels, batch), block(kMapsThreads);
-    if (dtype == PP_F16)
-        hipLaunchKernelGGL(k_flip_average_maps<__half>, grid, block, 0, stream, static_cast<const __half *>(net), n_samples, h, w,
-                           flip, static_cast<__half *>(ws), map_plane_stride(2, h, w));
-    else
-        hipLaunchKernelGGL(k_flip_average_maps<float>, grid, block, 0, stream, static_cast<const float *>(net), n_samples, h, w,
-                           flip, static_cast<float *>(ws), map_plane_stride(4, h, w));
-    return hipGetLastError();
-}
-
-hipError_t launch_heat_peaks_hbm(const void *ws, int dtype, int batch, int h, int w, int refine, int nms_mode, float thr, int maxp,
-                                 float4 *peaks, int *counts, unsigned *status, int *order, int *arrive_all, hipStream_t stream) {
-    const dim3 grid(PP_NUM_PART, batch), block(kThreads);
-    const size_t lds = lds_bytes_heat_hbm(h, w, maxp, batch);
-    if (dtype == PP_F16)
-        hipLaunchKernelGGL(k_heat_peaks_hbm<__half>, grid, block, lds, stream, static_cast<const __half *>(ws),
-                           map_plane_stride(2, h, w), h, w, refine, nms_mode, thr, maxp, peaks, counts, status, order, arrive_all);
-    else
-        hipLaunchKernelGGL(k_heat_peaks_hbm<float>, grid, block, lds, stream, static_cast<const float *>(ws),
-                           map_plane_stride(4, h, w), h, w, refine, nms_mode, thr, maxp, peaks, counts, status, order, arrive_all);
-    return hipGetLastError();
-}
-
-hipError_t launch_limb_connect_hbm(const void *ws, int dtype, int batch, int h, int w, int maxp, int cap, int min_img_size,
-                                   const int *min_img_size_dev, const float4 *peaks, const int *counts, float4 *conns, float4 *aux,
-                                   int *conn_counts, unsigned *status, const int *order, int *arrive, unsigned *ready,
-                                   pp_record *records, hipStream_t stream) {
-    const int nt = limb_threads();
-    const dim3 grid(PP_NUM_LIMB + (arrive ? 1 : 0), batch), block(nt);
-    const size_t lds = lds_bytes_limb_hbm(maxp, cap);
-#define PP_LAUNCH_LIMB(T, NT)                                                                                                       \
-    hipLaunchKernelGGL((k_limb_connect_hbm<T, NT>), grid, block, lds, stream, static_cast<const T *>(ws),                            \
-                       map_plane_stride(sizeof(T), h, w), h, w, maxp, cap, min_img_size, min_img_size_dev, peaks, counts, conns, aux, \
-                       conn_counts, status, order, arrive, ready, records)
-    if (dtype == PP_F16) {
-        if (nt == 512) PP_LAUNCH_LIMB(__half, 512);
-        else PP_LAUNCH_LIMB(__half, 256);
-    } else {
-        if (nt == 512) PP_LAUNCH_LIMB(float, 512);
-        else PP_LAUNCH_LIMB(float, 256);
-    }
-#undef PP_LAUNCH_LIMB
+    for_dtype(dtype, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL(k_flip_average_maps<T>, grid, block, 0, stream, static_cast<const T *>(net), n_samples, h, w, flip,
+                           static_cast<T *>(ws), map_plane_stride(sizeof(T), h, w));
+    });
     return hipGetLastError();
 }
 
@@ -3085,12 +2913,12 @@ hipError_t launch_limb_connect_hwc(const float *paf, int H, int W, int C, int ma
     return hipGetLastError();
 }
 
-hipError_t launch_assemble(int batch, int maxp, int explicit_ids, const float4 *peaks, const int *counts,
-                           const float4 *conns, const int *conn_counts, const unsigned *status, int flag_first,
-                           pp_record *records, hipStream_t stream) {
+hipError_t launch_assemble(int batch, int maxp, const float4 *peaks, const int *counts, const float4 *conns,
+                           const int *conn_counts, const unsigned *status, int flag_first, pp_record *records,
+                           hipStream_t stream) {
     const size_t lds = lds_bytes_assemble(maxp);
-    hipLaunchKernelGGL(k_assemble, dim3(batch), dim3(64), lds, stream, maxp, explicit_ids, peaks, counts, conns,
-                       conn_counts, status, flag_first, records);
+    hipLaunchKernelGGL(k_assemble, dim3(batch), dim3(64), lds, stream, maxp, peaks, counts, conns, conn_counts, status,
+                       flag_first, records);
     return hipGetLastError();
 }
 
@@ -3122,27 +2950,18 @@ hipError_t launch_limb_connect_py(const void *net, int dtype, int batch, int n_s
                                   int cap, int img_height, const int *img_height_dev, const float4 *peaks, const int *counts,
                                   void *conns, int *conn_counts, unsigned *status, const pp_test_cfg *cfg, hipStream_t stream) {
     const dim3 grid(PP_NUM_LIMB, batch), block(kThreads);
-    if (cfg_moves_limb(cfg)) {
-        const PyCfg k = make_py_cfg(*cfg);
-        if (dtype == PP_F16)
-            hipLaunchKernelGGL(k_limb_connect_py_cfg<__half>, grid, block, lds_bytes_limb_py(2, h, w, maxp, cap), stream,
-                               static_cast<const __half *>(net), n_samples, h, w, flip, maxp, cap, img_height, img_height_dev,
-                               peaks, counts, static_cast<double4 *>(conns), conn_counts, status, k);
+    for_dtype(dtype, [&](auto e) {
+        using T = decltype(e);
+        const size_t lds = lds_bytes_limb_py(sizeof(T), h, w, maxp, cap);
+        if (cfg_moves_limb(cfg))
+            hipLaunchKernelGGL(k_limb_connect_py_cfg<T>, grid, block, lds, stream, static_cast<const T *>(net), n_samples, h, w, flip,
+                               maxp, cap, img_height, img_height_dev, peaks, counts, static_cast<double4 *>(conns), conn_counts,
+                               status, make_py_cfg(*cfg));
         else
-            hipLaunchKernelGGL(k_limb_connect_py_cfg<float>, grid, block, lds_bytes_limb_py(4, h, w, maxp, cap), stream,
-                               static_cast<const float *>(net), n_samples, h, w, flip, maxp, cap, img_height, img_height_dev,
-                               peaks, counts, static_cast<double4 *>(conns), conn_counts, status, k);
-        return hipGetLastError();
-    }
-    if (dtype == PP_F16) {
-        hipLaunchKernelGGL(k_limb_connect_py<__half>, grid, block, lds_bytes_limb_py(2, h, w, maxp, cap), stream,
-                           static_cast<const __half *>(net), n_samples, h, w, flip, maxp, cap, img_height, img_height_dev,
-                           peaks, counts, static_cast<double4 *>(conns), conn_counts, status);
-    } else {
-        hipLaunchKernelGGL(k_limb_connect_py<float>, grid, block, lds_bytes_limb_py(4, h, w, maxp, cap), stream,
-                           static_cast<const float *>(net), n_samples, h, w, flip, maxp, cap, img_height, img_height_dev,
-                           peaks, counts, static_cast<double4 *>(conns), conn_counts, status);
-    }
+            hipLaunchKernelGGL(k_limb_connect_py<T>, grid, block, lds, stream, static_cast<const T *>(net), n_samples, h, w, flip,
+                               maxp, cap, img_height, img_height_dev, peaks, counts, static_cast<double4 *>(conns), conn_counts,
+                               status);
+    });
     return hipGetLastError();
 }
 
@@ -3182,13 +3001,38 @@ hipError_t launch_flip_average_planar(const void *net, int dtype, int batch, int
     const long total = (long)batch * PP_NUM_CH * h * w;
     long blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    if (dtype == PP_F16)
-        hipLaunchKernelGGL(k_flip_average_planar<__half>, dim3(blocks), dim3(256), 0, stream, static_cast<const __half *>(net),
-                           batch, h, w, flip, out);
-    else
-        hipLaunchKernelGGL(k_flip_average_planar<float>, dim3(blocks), dim3(256), 0, stream, static_cast<const float *>(net),
-                           batch, h, w, flip, out);
+    for_dtype(dtype, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL(k_flip_average_planar<T>, dim3(blocks), dim3(256), 0, stream, static_cast<const T *>(net), batch, h, w,
+                           flip, out);
+    });
     return hipGetLastError();
+}
+
+// One scale's set-up for an image of img_h x img_w, the ONE host copy of expressions the kernel evaluates too (bit-equal: the two
+// IEEE divisions as written).  Fills S.h .. S.sy and returns the rows / columns of the cropped x4 map U that a 32 x 32 output
+// tile's taps reach (ur x uc) and of the flip-averaged network output A those reach (ar x ac); ur == 0: the crop is empty.
+struct AccTiles {
+    int ur, uc, ar, ac;
+};
+static AccTiles acc_scale_setup(AccScale &S, int h, int w, int pad_down, int pad_right, int img_h, int img_w) {
+    S.h = h, S.w = w, S.ch = 4 * h - pad_down, S.cw = 4 * w - pad_right;
+    if (S.ch <= 0 || S.cw <= 0) return {0, 0, 0, 0};
+    S.identity = (S.ch == img_h && S.cw == img_w) ? 1 : 0;
+    S.sx = 1.0 / ((double)img_w / (double)S.cw);
+    S.sy = 1.0 / ((double)img_h / (double)S.ch);
+    const int ur = S.identity ? kAccTile : (int)(kAccTile * S.sy) + 6, uc = S.identity ? kAccTile : (int)(kAccTile * S.sx) + 6;
+    return {ur, uc, ur / 4 + 6, uc / 4 + 6};
+}
+template <typename Params>
+static void acc_params_head(Params &P, int n_scales, int flip, int img_h, int img_w, double *heat_acc, double *paf_acc) {
+    P.n = n_scales;
+    P.flip = flip;
+    P.img_h = img_h;
+    P.img_w = img_w;
+    P.n_div = (float)n_scales;
+    P.heat_acc = heat_acc;
+    P.paf_acc = paf_acc;
 }
 
 // One launch for all scales; PP_ERR-like failure (hipErrorInvalidValue) when a scale's tiles do not fit LDS (the caller then
@@ -3198,76 +3042,48 @@ hipError_t launch_accumulate_scales(int n_scales, const void *const *nets, int d
                                     double *paf_acc, hipStream_t stream) {
     if (n_scales < 1 || n_scales > kAccMaxScales) return hipErrorInvalidValue;
     AccParams P;
-    P.n = n_scales;
-    P.flip = flip;
-    P.img_h = img_h;
-    P.img_w = img_w;
-    P.n_div = (float)n_scales;
-    P.heat_acc = heat_acc;
-    P.paf_acc = paf_acc;
+    acc_params_head(P, n_scales, flip, img_h, img_w, heat_acc, paf_acc);
     int umax = 0, amax = 0;
     for (int i = 0; i < n_scales; i++) {
-        AccScale &S = P.s[i];
-        S.net = nets[i];
-        S.h = hs[i];
-        S.w = ws[i];
-        S.ch = 4 * hs[i] - pad_down[i];
-        S.cw = 4 * ws[i] - pad_right[i];
-        if (S.ch <= 0 || S.cw <= 0) return hipErrorInvalidValue;
-        S.identity = (S.ch == img_h && S.cw == img_w) ? 1 : 0;
-        S.sx = 1.0 / ((double)img_w / (double)S.cw);
-        S.sy = 1.0 / ((double)img_h / (double)S.ch);
-        const int ur = S.identity ? kAccTile : (int)(kAccTile * S.sy) + 6, uc = S.identity ? kAccTile : (int)(kAccTile * S.sx) + 6;
-        const int ar = ur / 4 + 6, ac = uc / 4 + 6;
-        umax = ur * uc > umax ? ur * uc : umax;
-        amax = ar * ac > amax ? ar * ac : amax;
+        P.s[i].net = nets[i];
+        const AccTiles t = acc_scale_setup(P.s[i], hs[i], ws[i], pad_down[i], pad_right[i], img_h, img_w);
+        if (!t.ur) return hipErrorInvalidValue;
+        umax = std::max(umax, t.ur * t.uc);
+        amax = std::max(amax, t.ar * t.ac);
     }
     P.u_cap = umax;
     P.a_cap = amax;
     const size_t lds = ((size_t)umax + amax) * sizeof(float);
     if (lds > 60000) return hipErrorInvalidValue;
     const dim3 grid(((img_w + kAccTile - 1) / kAccTile) * ((img_h + kAccTile - 1) / kAccTile), PP_NUM_CH, batch);
-    if (dtype == PP_F16) hipLaunchKernelGGL(k_accumulate_scales<__half>, grid, dim3(256), lds, stream, P);
-    else hipLaunchKernelGGL(k_accumulate_scales<float>, grid, dim3(256), lds, stream, P);
+    for_dtype(dtype, [&](auto e) {
+        hipLaunchKernelGGL(k_accumulate_scales<decltype(e)>, grid, dim3(256), lds, stream, P);
+    });
     return hipGetLastError();
 }
 
 // The same launch for a ragged bucket.  The host arrays serve the checks, the grid (the largest tile count of any image) and the
-// LDS capacities (the worst image of each scale, by the expressions above); the kernel reads the device copies.
+// LDS capacities (the worst image of each scale, by acc_scale_setup); the kernel reads the device copies.
 hipError_t launch_accumulate_scales_ragged(int n_scales, const void *const *nets, int dtype, int batch, const int *hs, const int *ws,
                                            int flip, const int *sizes, const int *sizes_dev, const int *pads, const int *pads_dev,
                                            long slot_area, double *heat_acc, double *paf_acc, hipStream_t stream) {
     if (n_scales < 1 || n_scales > kAccMaxScales) return hipErrorInvalidValue;
     AccParams P;
-    P.n = n_scales;
-    P.flip = flip;
-    P.img_h = P.img_w = 0;   // per image, from sizes_dev
-    P.n_div = (float)n_scales;
-    P.heat_acc = heat_acc;
-    P.paf_acc = paf_acc;
+    acc_params_head(P, n_scales, flip, 0, 0, heat_acc, paf_acc);   // image sizes: per image, from sizes_dev
     int umax = 0, amax = 0, tiles = 0;
     for (int b = 0; b < batch; b++) {
         const int t = ((sizes[batch + b] + kAccTile - 1) / kAccTile) * ((sizes[b] + kAccTile - 1) / kAccTile);
         tiles = t > tiles ? t : tiles;
     }
     for (int i = 0; i < n_scales; i++) {
-        AccScale &S = P.s[i];
-        S.net = nets[i];
-        S.h = hs[i];
-        S.w = ws[i];
-        S.ch = S.cw = S.identity = 0;   // per image, from pads_dev
-        S.sx = S.sy = 0.0;
         for (int b = 0; b < batch; b++) {
-            const int img_h = sizes[b], img_w = sizes[batch + b];
-            const int ch = 4 * hs[i] - pads[(i * 2) * batch + b], cw = 4 * ws[i] - pads[(i * 2 + 1) * batch + b];
-            if (ch <= 0 || cw <= 0) return hipErrorInvalidValue;
-            const int identity = (ch == img_h && cw == img_w) ? 1 : 0;
-            const double sx = 1.0 / ((double)img_w / (double)cw), sy = 1.0 / ((double)img_h / (double)ch);
-            const int ur = identity ? kAccTile : (int)(kAccTile * sy) + 6, uc = identity ? kAccTile : (int)(kAccTile * sx) + 6;
-            const int ar = ur / 4 + 6, ac = uc / 4 + 6;
-            umax = ur * uc > umax ? ur * uc : umax;
-            amax = ar * ac > amax ? ar * ac : amax;
+            AccScale one;
+            const AccTiles t = acc_scale_setup(one, hs[i], ws[i], pads[(i * 2) * batch + b], pads[(i * 2 + 1) * batch + b], sizes[b], sizes[batch + b]);
+            if (!t.ur) return hipErrorInvalidValue;
+            umax = std::max(umax, t.ur * t.uc);
+            amax = std::max(amax, t.ar * t.ac);
         }
+        P.s[i] = AccScale{nets[i], hs[i], ws[i], 0, 0, 0, 0.0, 0.0};   // crop, identity and scale factors: per image, from pads_dev
     }
     P.u_cap = umax;
     P.a_cap = amax;
@@ -3275,8 +3091,9 @@ hipError_t launch_accumulate_scales_ragged(int n_scales, const void *const *nets
     if (lds > 60000) return hipErrorInvalidValue;
     const AccRagged R{sizes_dev, pads_dev, slot_area};
     const dim3 grid(tiles, PP_NUM_CH, batch);
-    if (dtype == PP_F16) hipLaunchKernelGGL(k_accumulate_scales_ragged<__half>, grid, dim3(256), lds, stream, P, R);
-    else hipLaunchKernelGGL(k_accumulate_scales_ragged<float>, grid, dim3(256), lds, stream, P, R);
+    for_dtype(dtype, [&](auto e) {
+        hipLaunchKernelGGL(k_accumulate_scales_ragged<decltype(e)>, grid, dim3(256), lds, stream, P, R);
+    });
     return hipGetLastError();
 }
 
@@ -3294,32 +3111,19 @@ hipError_t launch_accumulate_scales_affine(int n_scales, const void *const *nets
                                         paf_acc, stream);
     if (n_scales < 1 || n_scales > kAccMaxScales) return hipErrorInvalidValue;
     AccParamsWarp P;
-    P.n = n_scales;
-    P.flip = flip;
-    P.img_h = img_h;
-    P.img_w = img_w;
-    P.n_div = (float)n_scales;
-    P.heat_acc = heat_acc;
-    P.paf_acc = paf_acc;
+    acc_params_head(P, n_scales, flip, img_h, img_w, heat_acc, paf_acc);
     long umax = 0, amax = 0, wmax = 0, rmax = 0, cmax = 0;
     for (int i = 0; i < n_scales; i++) {
         AccScaleWarp &S = P.s[i];
         S.net = nets[i];
-        S.h = hs[i];
-        S.w = ws[i];
-        S.ch = 4 * hs[i] - pad_down[i];
-        S.cw = 4 * ws[i] - pad_right[i];
-        if (S.ch <= 0 || S.cw <= 0) return hipErrorInvalidValue;
-        S.identity = (S.ch == img_h && S.cw == img_w) ? 1 : 0;
-        S.sx = 1.0 / ((double)img_w / (double)S.cw);
-        S.sy = 1.0 / ((double)img_h / (double)S.ch);
-        const int ur = S.identity ? kAccTile : (int)(kAccTile * S.sy) + 6, uc = S.identity ? kAccTile : (int)(kAccTile * S.sx) + 6;
+        const AccTiles t = acc_scale_setup(S, hs[i], ws[i], pad_down[i], pad_right[i], img_h, img_w);
+        if (!t.ur) return hipErrorInvalidValue;
+        const int ur = t.ur, uc = t.uc;
         S.warp = m_inv[i] ? 1 : 0;
         for (int k = 0; k < 6; k++) S.m[k] = m_inv[i] ? m_inv[i][k] : 0.0;
         if (!S.warp) {
-            const int ar = ur / 4 + 6, ac = uc / 4 + 6;
             umax = std::max(umax, (long)ur * uc);
-            amax = std::max(amax, (long)ar * ac);
+            amax = std::max(amax, (long)t.ar * t.ac);
             continue;
         }
         const double *m = m_inv[i];
@@ -3351,8 +3155,9 @@ hipError_t launch_accumulate_scales_affine(int n_scales, const void *const *nets
     P.w_cap = (int)wmax;
     P.r_cap = (int)rmax;
     const dim3 grid(((img_w + kAccTile - 1) / kAccTile) * ((img_h + kAccTile - 1) / kAccTile), PP_NUM_CH, batch);
-    if (dtype == PP_F16) hipLaunchKernelGGL(k_accumulate_scales_affine<__half>, grid, dim3(256), lds, stream, P);
-    else hipLaunchKernelGGL(k_accumulate_scales_affine<float>, grid, dim3(256), lds, stream, P);
+    for_dtype(dtype, [&](auto e) {
+        hipLaunchKernelGGL(k_accumulate_scales_affine<decltype(e)>, grid, dim3(256), lds, stream, P);
+    });
     return hipGetLastError();
 }
 

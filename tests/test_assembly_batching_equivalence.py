@@ -1,5 +1,5 @@
-"""CPU: the order-preserving batching the assembly kernels apply (csrc/posepaf_kernels.hip: k_assemble for the drop-in path,
-assemble_image_wave -- stable slots + counting classification -- for the batched path) against the plain
+"""CPU: the order-preserving batching the batched path's assembly applies (csrc/posepaf_kernels.hip: assemble_image_wave --
+stable slots + counting classification; the drop-in path's k_assemble IS the plain loop) against the plain
 connection-by-connection loop of the reference (pafprocess.cpp:138-275), both restated in Python on random inputs that are
 far nastier than real scenes (few peaks per part, so skeletons share peaks, merge, and the `id > 0` membership quirk sums
 real ids into ids that belong to other peaks).  What is checked is the ARGUMENT the kernel relies on:
@@ -85,6 +85,7 @@ def assemble_reference(conns, ps):
 
 
 def assemble_batched(conns, ps, off, cnt, stats):
+    """the argument in its plainest form (owner tables, physical erase); no kernel runs this form any more"""
     skel = []
     for limb, (part1, part2) in enumerate(LIMBS):
         cs = conns[limb]

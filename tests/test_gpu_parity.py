@@ -284,6 +284,52 @@ def test_dropin_process_paf_against_compiled_reference(torch_cuda, oracle, refer
             assert np.float32(pafprocess.get_part_score(cid)) == want["peaks"][cid, 2]
 
 
+def _dropin_equals(jl, up, want, ctx):
+    """utils.pafprocess.process_paf on (jl, up): ids, scores and the part getters equal `want`'s; -> the ids"""
+    from utils.pafprocess import pafprocess
+    assert pafprocess.process_paf(jl[None], up, 512) == 0, ctx
+    nh = pafprocess.get_num_humans()
+    assert nh == len(want["ids"]), ctx
+    ids = np.array([[pafprocess.get_part_peak_id(h, p) for p in range(18)] for h in range(nh)]).reshape(nh, 18)
+    assert np.array_equal(ids, want["ids"]), ctx
+    sc = np.array([pafprocess.get_score(h) for h in range(nh)], np.float32)
+    assert np.array_equal(sc, want["scores"]), ctx
+    assert len(want["peaks"]) == len(jl), ctx
+    for cid in range(len(jl)):
+        assert pafprocess.get_part_x(cid) == want["peaks"][cid, 0], ctx
+        assert pafprocess.get_part_y(cid) == want["peaks"][cid, 1], ctx
+        assert np.float32(pafprocess.get_part_score(cid)) == want["peaks"][cid, 2], ctx
+    return ids
+
+
+def test_dropin_id_summing_merge(torch_cuda, oracle, reference_cpp):
+    """The drop-in assembly on the hand-built scene whose merge ADDS two peak ids (pafprocess.cpp:200-228, 1 + 0 + 1 = 2) and
+    whose later connection of the same limb meets the made-up id: one human, nose id 2, as the reference's own C++ gives."""
+    from posepaf import synth
+    heat, paf = oracle.flip_average(synth.make_id_sum_merge_scene(), flip=False)
+    jl, _ = oracle.heatmap_nms(heat)
+    up = oracle.upsample4_hwc(paf)
+    ids = _dropin_equals(jl, up, reference_cpp.process_paf(jl[None], up, 512), "id-sum merge")
+    assert ids.shape == (1, 18) and ids[0, 0] == 2
+
+
+def test_dropin_rows_out_of_part_order(torch_cuda, oracle, reference_cpp):
+    """The joint list regrouped part 17 first ... part 0 last (order inside a part kept).  process_paf numbers peaks by input
+    row (pafprocess.cpp:34) and indexes the part-bucketed line BY that id (:162), so here a peak's id differs from its position
+    in the line for almost every peak -- the case the .w ids exist for.  Seed 11: the oracle reports no sort_oob for these rows."""
+    from posepaf import synth
+    heat, paf = oracle.flip_average(synth.make_net_output(6, 11, dtype=np.float32))
+    jl, _ = oracle.heatmap_nms(heat)
+    up = oracle.upsample4_hwc(paf)
+    rows = np.ascontiguousarray(jl[np.argsort(-jl[:, 4], kind="stable")])
+    line_pos = np.argsort(np.argsort(rows[:, 4], kind="stable"), kind="stable")   # position of input row i in the bucketed line
+    assert np.count_nonzero(line_pos != np.arange(len(rows))) >= 0.9 * len(rows)
+    want = oracle.process_paf(rows[None], up, 512)
+    assert not want["sort_oob"] and len(want["ids"]) > 0
+    _dropin_equals(rows, up, want, "rows out of part order, oracle")
+    _dropin_equals(rows, up, reference_cpp.process_paf(rows[None], up, 512), "rows out of part order, compiled reference")
+
+
 def test_dropin_argument_errors(torch_cuda):
     from posepaf import _lib
     from utils.pafprocess import pafprocess

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Confirms that the hand-built id-summing merge scene takes K_C's table-abandon branch (diagnostic stamps); GPU only."""
+"""Confirms that the hand-built id-summing merge scene takes the table-abandon branch of the wave assembly
+(assemble_image_wave, reached through post.process; its diagnostic stamps); GPU only."""
 import ctypes as C
 import os
 import sys
