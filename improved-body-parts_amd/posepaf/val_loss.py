@@ -3,6 +3,7 @@ stacks and scales (models/loss_model.py:23-81, :133-161) as per-image terms, the
 
     terms = focal_l2_terms(preds, target)          # device float64 (T, K, B): stack, scale, image
     loss = combine(terms)                          # 0-d device float64: the scalar MultiTaskLoss.forward returns
+    loss.backward()                                # when a prediction requires grad: pp_focal_l2_grad (focal_l2_grad is the raw entry)
     meter = ValLossMeter(); meter.update(terms); meter.summary()
 
 preds is what FusedIMHN.forward(x, all_preds=True) returns (or any list of lists of (B, 50, h_s, w_s) device tensors), target what
@@ -98,21 +99,9 @@ def workspace_bytes(batch: int, n_stacks: int, sizes) -> int:
     return n
 
 
-def focal_l2_terms(preds, target, mask=None, multi_task_weight: float = MULTI_TASK_WEIGHT, keypoint_task_weight: float = KEYPOINT_TASK_WEIGHT,
-                   plain_l2: bool = False, out=None, workspace=None, stream=None):
-    """preds[t][s]: device (B, 50, h_s, w_s) float16 / float32 -- planes, channels_last or the [:, :50] view of a fused head's
-    64-channel output are read where they lie, anything else through a contiguous copy; target: device (B, 50, H, W), or
-    (B, n, 50, H, W) of which sample 0 is read in place; mask: device float32 (B, H, W) or None (all ones).
-    -> device float64 (T, K, B).  plain_l2: the reference's l2_loss (no focal factor).  out / workspace (uint8, at least
-    workspace_bytes): reuse these; stream: a torch stream (default: the current one).  Asynchronous."""
-    import torch
-    T, K, B, H, W, sizes, dtype = _check_args(preds, target, mask, out, workspace)
-    if not (float(multi_task_weight) == float(multi_task_weight) and float(keypoint_task_weight) == float(keypoint_task_weight)):
-        raise PosePafError("the task weights must be numbers")
-    from . import _lib
-    L = _lib.load()
-    dev = target.device
-    esz = 2 if dtype == torch.float16 else 4
+def _prepare(preds, target, mask, T, K, H, W, esz):
+    """-> target and its image stride as the library reads them, the contiguous mask, keep[s][t] (the tensors the kernel reads: the
+    caller's where their layout is one it takes, contiguous copies elsewhere), layout[s] and {layout: [scales]}"""
     if target.dim() == 5:
         image_stride = int(target.shape[1]) * sk.NUM_CH * H * W
         if not target.is_contiguous():
@@ -130,6 +119,23 @@ def focal_l2_terms(preds, target, mask=None, multi_task_weight: float = MULTI_TA
     groups = {}
     for s in range(K):
         groups.setdefault(layout[s], []).append(s)
+    return target, image_stride, mask, keep, layout, groups
+
+
+def _check_weights(multi_task_weight, keypoint_task_weight):
+    if not (float(multi_task_weight) == float(multi_task_weight) and float(keypoint_task_weight) == float(keypoint_task_weight)):
+        raise PosePafError("the task weights must be numbers")
+
+
+def _terms(shape, preds, target, mask, multi_task_weight, keypoint_task_weight, plain_l2, out, workspace, stream):
+    """focal_l2_terms behind its argument checks"""
+    import torch
+    T, K, B, H, W, sizes, dtype = shape
+    from . import _lib
+    L = _lib.load()
+    dev = target.device
+    esz = 2 if dtype == torch.float16 else 4
+    target, image_stride, mask, keep, layout, groups = _prepare(preds, target, mask, T, K, H, W, esz)
     if out is None:
         out = torch.empty((T, K, B), dtype=torch.float64, device=dev)
     need = max(workspace_bytes(B, T, [sizes[s] for s in members]) for members in groups.values())
@@ -154,6 +160,116 @@ def focal_l2_terms(preds, target, mask=None, multi_task_weight: float = MULTI_TA
             if not whole:
                 out[:, members] = dst
     return out
+
+
+def focal_l2_terms(preds, target, mask=None, multi_task_weight: float = MULTI_TASK_WEIGHT, keypoint_task_weight: float = KEYPOINT_TASK_WEIGHT,
+                   plain_l2: bool = False, out=None, workspace=None, stream=None):
+    """preds[t][s]: device (B, 50, h_s, w_s) float16 / float32 -- planes, channels_last or the [:, :50] view of a fused head's
+    64-channel output are read where they lie, anything else through a contiguous copy; target: device (B, 50, H, W), or
+    (B, n, 50, H, W) of which sample 0 is read in place; mask: device float32 (B, H, W) or None (all ones).
+    -> device float64 (T, K, B).  plain_l2: the reference's l2_loss (no focal factor).  out / workspace (uint8, at least
+    workspace_bytes): reuse these; stream: a torch stream (default: the current one).  Asynchronous.
+    Differentiable with respect to the predictions: with grad mode on and a prediction that requires grad the result is an autograd
+    node whose backward is focal_l2_grad (once differentiable; `out` is refused there, and so is a target or mask that requires
+    grad: the loss has no derivative with respect to either).  Otherwise the result has no grad_fn."""
+    import torch
+    shape = _check_args(preds, target, mask, out, workspace)
+    _check_weights(multi_task_weight, keypoint_task_weight)
+    if torch.is_grad_enabled() and any(p.requires_grad for stack in preds for p in stack):
+        if out is not None:
+            raise PosePafError("out= cannot receive a result that autograd tracks: leave it out when a prediction requires grad")
+        if target.requires_grad or (mask is not None and mask.requires_grad):
+            raise PosePafError("the loss has no gradient with respect to the target or the mask: detach them")
+        T, K, dtype = shape[0], shape[1], shape[6]
+        # a layout the kernel does not take becomes a contiguous copy HERE, outside the node: torch differentiates the copy
+        keep = _prepare(preds, target, mask, T, K, shape[3], shape[4], 2 if dtype == torch.float16 else 4)[3]
+        flat = [keep[s][t] for t in range(T) for s in range(K)]
+        return _function()(target, mask, shape, float(multi_task_weight), float(keypoint_task_weight), bool(plain_l2), workspace, stream, *flat)
+    return _terms(shape, preds, target, mask, multi_task_weight, keypoint_task_weight, plain_l2, out, workspace, stream)
+
+
+def focal_l2_grad(preds, target, term_weights, mask=None, multi_task_weight: float = MULTI_TASK_WEIGHT,
+                  keypoint_task_weight: float = KEYPOINT_TASK_WEIGHT, plain_l2: bool = False, stream=None):
+    """The gradient of sum(term_weights * focal_l2_terms(preds, target, mask, ...)) with respect to every prediction
+    (pp_focal_l2_grad; the arithmetic: INTEGRATION section 16).  term_weights: device float64 (T, K, B); a zero masks an image.
+    -> grads[t][s], each with the shape, dtype and strides of preds[t][s]: planes and channels_last tensors get a buffer of their
+    own geometry; the [:, :50] view of an S-channel pixel-major tensor gets the same view of a fresh S-channel buffer whose padding
+    channels are zeroed once here (the kernel never writes them); any other layout is read through a contiguous copy and gets a
+    contiguous gradient.  Nothing is tracked by autograd.  Asynchronous."""
+    import torch
+    T, K, B, H, W, sizes, dtype = _check_args(preds, target, mask, None, None)
+    _check_weights(multi_task_weight, keypoint_task_weight)
+    if not isinstance(term_weights, torch.Tensor) or tuple(term_weights.shape) != (T, K, B) or term_weights.dtype != torch.float64:
+        raise PosePafError(f"term_weights must be a float64 ({T}, {K}, {B}) tensor")
+    if not term_weights.is_cuda or term_weights.device != target.device:
+        raise PosePafError(f"term_weights must live on the target's device {target.device}: focal_l2_grad has no CPU path")
+    from . import _lib
+    L = _lib.load()
+    dev = target.device
+    esz = 2 if dtype == torch.float16 else 4
+    with torch.no_grad():
+        target, image_stride, mask, keep, layout, groups = _prepare(preds, target, mask, T, K, H, W, esz)
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        flags = LOSS_PLAIN_L2 if plain_l2 else 0
+        grads = [[None] * K for _ in range(T)]
+        with torch.cuda.device(dev), torch.cuda.stream(st):
+            tw = term_weights.detach().contiguous()
+            for stride, members in groups.items():
+                k = len(members)
+                for s in members:
+                    h, w = sizes[s]
+                    for t in range(T):
+                        if stride == 0:
+                            grads[t][s] = torch.empty((B, sk.NUM_CH, h, w), dtype=dtype, device=dev)
+                        else:
+                            buf = torch.empty((B, h, w, stride), dtype=dtype, device=dev)
+                            if stride > sk.NUM_CH:
+                                buf[..., sk.NUM_CH:].zero_()
+                            grads[t][s] = buf.permute(0, 3, 1, 2)[:, :sk.NUM_CH]
+                part = tw if k == K else tw[:, members].contiguous()
+                table = (C.c_void_p * (T * k))(*[keep[s][t].data_ptr() for t in range(T) for s in members])
+                gtable = (C.c_void_p * (T * k))(*[grads[t][s].data_ptr() for t in range(T) for s in members])
+                hs, ws = (C.c_int * k)(*[sizes[s][0] for s in members]), (C.c_int * k)(*[sizes[s][1] for s in members])
+                _lib.check(L.pp_focal_l2_grad(
+                    table, PP_F16 if dtype == torch.float16 else PP_F32, int(stride), C.c_void_p(target.data_ptr()),
+                    PP_F16 if target.dtype == torch.float16 else PP_F32, image_stride, C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                    B, H, W, T, k, hs, ws, float(multi_task_weight), float(keypoint_task_weight), flags, C.c_void_p(part.data_ptr()),
+                    gtable, C.c_void_p(st.cuda_stream)))
+    return grads
+
+
+_FUNCTION = None
+
+
+def _function():
+    """the autograd node of focal_l2_terms (built on first use: this module imports without torch)"""
+    global _FUNCTION
+    if _FUNCTION is not None:
+        return _FUNCTION
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class FocalL2Terms(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, target, mask, shape, multi_task_weight, keypoint_task_weight, plain_l2, workspace, stream, *flat):
+            T, K = shape[0], shape[1]
+            preds = [[flat[t * K + s] for s in range(K)] for t in range(T)]
+            ctx.save_for_backward(target, mask, *flat)
+            ctx.call = (T, K, multi_task_weight, keypoint_task_weight, plain_l2, stream)
+            return _terms(shape, preds, target, mask, multi_task_weight, keypoint_task_weight, plain_l2, None, workspace, stream)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_terms):
+            T, K, multi_task_weight, keypoint_task_weight, plain_l2, stream = ctx.call
+            target, mask, *flat = ctx.saved_tensors
+            preds = [[flat[t * K + s] for s in range(K)] for t in range(T)]
+            grads = focal_l2_grad(preds, target, grad_terms, mask, multi_task_weight, keypoint_task_weight, plain_l2, stream)
+            wanted = ctx.needs_input_grad[8:]
+            return (None,) * 8 + tuple(grads[t][s] if wanted[t * K + s] else None for t in range(T) for s in range(K))
+
+    _FUNCTION = FocalL2Terms.apply
+    return _FUNCTION
 
 
 def _weights(values, n, name, ref):

@@ -486,6 +486,30 @@ PP_API int pp_focal_l2_terms(const void *const *pred_dev, int pred_dtype, int pr
                              const int *hs, const int *ws, double multi_task_weight, double keypoint_task_weight, int flags,
                              void *workspace_dev, double *terms_dev, void *stream);
 
+/* The derivative of pp_focal_l2_terms with respect to the predictions: for upstream weights tw[t][s][b] = dL / dterms[t][s][b]
+ *   d = p - (double)G
+ *   focal:  f = |1 - st|,  f' = -sgn(1 - p) where G >= 0.01f, sgn(p) elsewhere, sgn(0) = +0.0 (torch's abs backward)
+ *           e = (2.0 d) f + (d d) f'
+ *   plain (PP_LOSS_PLAIN_L2):  e = 2.0 d
+ *   grad = tw[t][s][b] (cw[c] (M e))       float64 in exactly this association, no contraction
+ * rounded to float32 (nearest even) and, for PP_F16 predictions, that float32 rounded to binary16.  G, M, cw and every argument up to
+ * `flags` are pp_focal_l2_terms's.  There is no gradient with respect to the target or the mask (the foreground test and the mask
+ * threshold are steps).
+ *   term_weight_dev  DEVICE double[n_stacks][n_scales][batch], 8-byte aligned; a zero weight gives a zero gradient (a padded batch)
+ *   grad_dev     HOST array of n_stacks * n_scales DEVICE pointers, [t * n_scales + s] -> a buffer with the geometry and dtype of
+ *                pred_dev[t * n_scales + s] (planes, or pixel-major with the same stride); must not be the prediction itself
+ * Every element of channels 0..49 is stored plainly on every launch (no memset, no atomics, no workspace); the padding channels
+ * 50 .. stride - 1 of a pixel-major buffer and everything behind channel 49 of the last pixel are never written.  Stores are 16 bytes
+ * wide where pp_focal_l2_terms's loads are and the gradient pointers of the scale are 16-byte aligned too, element by element
+ * elsewhere.  Elementwise: an image's gradients do not depend on batch size, slot, alignment or launch geometry.
+ * Refuses what pp_focal_l2_terms refuses, with the same codes, and with PP_ERR_BAD_ARG a null term_weight_dev / grad_dev / entry of
+ * it, a gradient pointer not aligned to its element, term_weight_dev off an 8-byte boundary, and a gradient pointer equal to its
+ * prediction's.  Nothing is launched on a refusal.  Asynchronous, nothing allocated, needs no context: capturable. */
+PP_API int pp_focal_l2_grad(const void *const *pred_dev, int pred_dtype, int pred_pixel_stride, const void *target_dev, int target_dtype,
+                            long long target_image_stride, const float *mask_dev, int batch, int H, int W, int n_stacks, int n_scales,
+                            const int *hs, const int *ws, double multi_task_weight, double keypoint_task_weight, int flags,
+                            const double *term_weight_dev, void *const *grad_dev, void *stream);
+
 /* A2 standalone: the arrays predict_refactor returns (utils/parse_skeletons.py:82-103).  net_out_dev as for
  * pp_process_batch; heat_hwc_dev: DEVICE float[batch][h][w][20], paf_hwc_dev: DEVICE float[batch][h][w][30]. */
 PP_API int pp_flip_average(const void *net_out_dev, int dtype, int batch, int h, int w, int flip, float *heat_hwc_dev,
