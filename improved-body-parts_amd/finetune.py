@@ -3,6 +3,7 @@
 
     python finetune.py --synthetic 64 --batch 8 --sizes 128x128 --steps 20 \\
         [--stages 4] [--train all|heads] [--lr 2.5e-5] [--loss device|torch] [-p weights.pth] [--seed 0] [--save out.pth]
+        [--augment [--src_sizes HxW[,HxW...]]]
 
 Per step: a batch of synthetic images (random uint8 pixels, divided by 255 on the device by pp_preprocess_u8) and their
 synth.random_people joints; the targets rendered from the joints by pp_render_scenes (one sample, no noise, reverse_kp, as
@@ -16,9 +17,17 @@ evaluate.py -p loads); val_loss.focal_l2_terms -> combine -> backward() (pp_foca
   --loss torch    a torch formulation of the same contract (windows summed in float64 and rounded once to
                   float32, the foreground test in float32, everything behind in float64) differentiated by torch -- for A/B
   -p              a reference checkpoint (.pth with a 'weights' entry); without one the deterministic initialisation
+  --augment       the reference's data transformer on the device (posepaf/augment.py, pp_augment_batch) in front of every step: per
+                  step and image an AugmentSelection.random drawn from random.Random seeded by --seed and the step (tint_prob = 0:
+                  the colour distortion is out of scope) warps the raw uint8 image and its two masks to --sizes, maps the joints, and
+                  the loss takes mask = mask_miss (--loss torch takes the same mask).  --src_sizes gives the source sizes (image i
+                  has the (i mod n)-th; default: --sizes), ragged in one slot.  Synthetic masks: mask_miss is 255 with a few seeded
+                  zero rectangles, mask_all 255 inside each person's joint bounding box; objpos is the centre of person 0's box and
+                  scale_provided that box's height over the output height.  The targets are rendered from the transformed joints
+                  and channel 48 receives the eroded mask_all plane after the render (the renderer zeroes that channel)
 
 Prints one JSON line: losses (per step), loss_first, loss_last, grad_norm_first (L2 norm of the updated parameters' gradients at
-step 0), seconds, loss, train, images_per_step.  Combinations it does not support end with a message before the GPU is touched.
+step 0), seconds, loss, train, images_per_step (and "augment": true with --augment).  Combinations it does not support end with a message before the GPU is touched.
 """
 import argparse
 import ctypes as C
@@ -50,7 +59,20 @@ def parse(argv=None):
     ap.add_argument("-p", "--checkpoint_path", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save", default=None, help="write {'weights': state_dict} here after the last step")
+    ap.add_argument("--augment", action="store_true", help="run the device data transformer in front of every step")
+    ap.add_argument("--src_sizes", default=None, help="with --augment: source sizes HxW[,HxW...] (default: --sizes)")
     return ap.parse_args(argv)
+
+
+def parse_src_sizes(text):
+    """'80x96,64x64' -> [(80, 96), (64, 64)], None when it is not such a list"""
+    try:
+        sizes = [tuple(int(v) for v in item.lower().split("x")) for item in text.split(",")]
+    except ValueError:
+        return None
+    if not sizes or any(len(s) != 2 or not (8 <= s[0] <= 32768 and 8 <= s[1] <= 32768) for s in sizes):
+        return None
+    return sizes
 
 
 def refusals(a):
@@ -58,7 +80,7 @@ def refusals(a):
     from posepaf._lib import LOSS_MAX_STACKS
     out = []
     if a.synthetic < 1:
-        out.append("--synthetic N (N >= 1) is the only data source: the data transformer of the reference is not part of this script")
+        out.append("--synthetic N (N >= 1) is the only data source: the reference's HDF5 dataset reader is not part of this script")
     if a.batch < 1 or a.steps < 1:
         out.append("--batch and --steps must be at least 1")
     sizes = a.sizes.split(",")
@@ -70,6 +92,10 @@ def refusals(a):
         out.append("--sizes takes one size: a step is one batch of equally sized images")
     elif h < 64 or w < 64 or h % 64 or w % 64:
         out.append(f"--sizes {a.sizes}: both sides must be positive multiples of 64 (the coarsest of the five scales is 1/64 of the image)")
+    if a.src_sizes is not None and not a.augment:
+        out.append("--src_sizes belongs to --augment: without it the images have the one size of --sizes")
+    elif a.augment and parse_src_sizes(a.src_sizes if a.src_sizes is not None else a.sizes) is None:
+        out.append(f"--src_sizes {a.src_sizes}: a comma-separated list of HxW with both sides in 8..32768")
     if not 1 <= a.stages <= LOSS_MAX_STACKS:
         out.append(f"--stages must be 1..{LOSS_MAX_STACKS} (the loss kernel walks at most {LOSS_MAX_STACKS} stacks)")
     if not (a.lr > 0 and a.lr == a.lr and a.lr != float("inf")):
@@ -81,8 +107,9 @@ def refusals(a):
     return out
 
 
-def torch_terms(torch, preds, target):
-    """the contract of pp_focal_l2_terms on stock operators, without a mask -> (T, K, B) float64 that torch differentiates"""
+def torch_terms(torch, preds, target, mask=None):
+    """the contract of pp_focal_l2_terms on stock operators -> (T, K, B) float64 that torch differentiates.  mask: float32 (B, H, W)
+    or None, resampled bilinearly (align_corners = False) in float64 with values < 0.5 set to 0"""
     import torch.nn.functional as F
     from posepaf.val_loss import KEYPOINT_TASK_WEIGHT, MULTI_TASK_WEIGHT
     cw = torch.ones(50, dtype=torch.float64, device=target.device)
@@ -97,6 +124,9 @@ def torch_terms(torch, preds, target):
             p = pred.double()
             d = p - G.double()
             v = d * d * torch.abs(1.0 - torch.where(fg, p, 1.0 - p)) * cw[None, :, None, None]
+            if mask is not None:
+                M = F.interpolate(mask[:, None].double(), size=tuple(pred.shape[-2:]), mode="bilinear", align_corners=False)
+                v = v * torch.where(M < 0.5, torch.zeros_like(M), M)
             row.append(v.sum(dim=(1, 2, 3)))
         rows.append(torch.stack(row))
     return torch.stack(rows)
@@ -122,6 +152,43 @@ def forward(pn, x, heads_only):
                 caches = [pn.merge_preds[t][s](pn.outs[t][s](feats[s])) + pn.merge_features[t][s](feats[s]) for s in range(pn.num_scales)]
                 y = y + caches[0]
     return [[head(f) for head, f in zip(pn.outs[t], feats_of[t])] for t in range(pn.num_stages)]
+
+
+def augment_data(a, H, W):
+    """--augment's N synthetic samples on the host: uint8 images and masks in one slot, sizes (2, N), float64 joints, n_people, objpos,
+    scale_provided.  Image i has the (i mod n)-th source size; its people are synth.random_people of that size."""
+    from posepaf import synth, synth_device
+    src = parse_src_sizes(a.src_sizes if a.src_sizes is not None else a.sizes)
+    N = a.synthetic
+    slot_h, slot_w = max(s[0] for s in src), max(s[1] for s in src)
+    images, mask_miss = np.zeros((N, slot_h, slot_w, 3), np.uint8), np.zeros((N, slot_h, slot_w), np.uint8)
+    mask_all, sizes = np.zeros((N, slot_h, slot_w), np.uint8), np.zeros((2, N), np.int32)
+    people, objpos, scale_provided = [], [], []
+    for i in range(N):
+        h, w = src[i % len(src)]
+        sizes[:, i] = h, w
+        images[i, :h, :w] = np.frombuffer(np.random.default_rng(10_000 + 1000 * a.seed + i).bytes(h * w * 3), np.uint8).reshape(h, w, 3)
+        pj = synth.random_people(PEOPLE[i % len(PEOPLE)], np.random.default_rng(20_000 + 1000 * a.seed + i), img_h=h, img_w=w)
+        people.append(pj)
+        rng = np.random.default_rng(30_000 + 1000 * a.seed + i)
+        mask_miss[i, :h, :w] = 255
+        for _ in range(3):                                       # a few zero rectangles: regions without annotation
+            y, x = int(rng.integers(0, h)), int(rng.integers(0, w))
+            mask_miss[i, y:min(h, y + int(rng.integers(4, 1 + max(4, h // 4)))), x:min(w, x + int(rng.integers(4, 1 + max(4, w // 4))))] = 0
+        boxes = []
+        for p in pj:
+            xy = p[p[:, 2] < 2, :2]
+            if len(xy) == 0:
+                continue
+            x0, y0, x1, y1 = xy[:, 0].min(), xy[:, 1].min(), xy[:, 0].max(), xy[:, 1].max()
+            boxes.append((x0, y0, x1, y1))
+            mask_all[i, max(0, int(np.floor(y0))):min(h, int(np.ceil(y1)) + 1), max(0, int(np.floor(x0))):min(w, int(np.ceil(x1)) + 1)] = 255
+        x0, y0, x1, y1 = boxes[0] if boxes else (0.0, 0.0, float(w), float(h))
+        objpos.append(((x0 + x1) / 2, (y0 + y1) / 2))
+        scale_provided.append(max(float(y1 - y0), 1.0) / H)
+    joints = np.zeros((N, max(PEOPLE), 18, 3), np.float64)
+    joints, n_people = synth_device.pack_joints(people, max(PEOPLE), joints_out=joints)
+    return images, mask_miss, mask_all, sizes, joints, n_people, objpos, scale_provided
 
 
 def main(argv=None):
@@ -151,10 +218,17 @@ def main(argv=None):
     opt = torch.optim.SGD(params, lr=a.lr, momentum=MOMENTUM, weight_decay=WEIGHT_DECAY)
 
     # the data: N images and their people, staged on the device once
-    images = np.stack([np.frombuffer(np.random.default_rng(10_000 + 1000 * a.seed + i).bytes(H * W * 3), np.uint8).reshape(H, W, 3)
-                       for i in range(N)])
-    people = [synth.random_people(PEOPLE[i % len(PEOPLE)], np.random.default_rng(20_000 + 1000 * a.seed + i), img_h=H, img_w=W) for i in range(N)]
-    joints, n_people = synth_device.pack_joints(people, max(PEOPLE))
+    if a.augment:
+        import random
+        from posepaf import augment
+        images, mask_miss, mask_all, sizes, joints, n_people, objpos, scale_provided = augment_data(a, H, W)
+        mask_miss, mask_all, sizes = torch.from_numpy(mask_miss).to(dev), torch.from_numpy(mask_all).to(dev), torch.from_numpy(sizes).to(dev)
+        draw_params = augment.TransformParams(tint_prob=0.0)      # the colour distortion is out of scope: never drawn
+    else:
+        images = np.stack([np.frombuffer(np.random.default_rng(10_000 + 1000 * a.seed + i).bytes(H * W * 3), np.uint8).reshape(H, W, 3)
+                           for i in range(N)])
+        people = [synth.random_people(PEOPLE[i % len(PEOPLE)], np.random.default_rng(20_000 + 1000 * a.seed + i), img_h=H, img_w=W) for i in range(N)]
+        joints, n_people = synth_device.pack_joints(people, max(PEOPLE))
     images, joints, n_people = torch.from_numpy(images).to(dev), torch.from_numpy(joints).to(dev), torch.from_numpy(n_people).to(dev)
 
     # step k takes images k, k + ceil(N / B), k + 2 ceil(N / B) ...: the people of an image rise with its index (PEOPLE), so consecutive
@@ -165,13 +239,26 @@ def main(argv=None):
     t0 = time.perf_counter()
     for step in range(a.steps):
         idx = (step + torch.arange(B, device=dev) * per_pass) % N
-        raw, x = images[idx], torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
-        _lib.check(L.pp_preprocess_u8(C.c_void_p(raw.data_ptr()), C.c_void_p(x.data_ptr()), _lib.PP_F32, B, H, W, 64, 0, 0,
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        target = synth_device.render_scenes(joints[idx], n_people[idx], H // 4, W // 4, dtype=torch.float16, flip=False, noise=0.0,
-                                            reverse_kp=True)
+        mask = None
+        if a.augment:
+            # raw uint8 slots -> (x, target, mask) on the device; the draws and the matrices are the only host work
+            rng = random.Random(1_000_003 * a.seed + step)
+            host_idx = [(step + i * per_pass) % N for i in range(B)]
+            augs = [augment.AugmentSelection.random(draw_params, rng) for _ in range(B)]
+            x, mask, fg, moved = augment.transform_batch(images[idx], mask_miss[idx], mask_all[idx], sizes[:, idx].contiguous(), joints[idx],
+                                                         n_people[idx], augs, [objpos[i] for i in host_idx],
+                                                         [scale_provided[i] for i in host_idx], (H, W))
+            target = synth_device.render_scenes(moved, n_people[idx], H // 4, W // 4, dtype=torch.float16, flip=False, noise=0.0,
+                                                reverse_kp=True)
+            target[:, 0, 48].copy_(fg)                            # after the render, on the same stream: the renderer zeroes channel 48
+        else:
+            raw, x = images[idx], torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+            _lib.check(L.pp_preprocess_u8(C.c_void_p(raw.data_ptr()), C.c_void_p(x.data_ptr()), _lib.PP_F32, B, H, W, 64, 0, 0,
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            target = synth_device.render_scenes(joints[idx], n_people[idx], H // 4, W // 4, dtype=torch.float16, flip=False, noise=0.0,
+                                                reverse_kp=True)
         preds = forward(pn, x, heads)
-        terms = val_loss.focal_l2_terms(preds, target) if a.loss == "device" else torch_terms(torch, preds, target[:, 0])
+        terms = val_loss.focal_l2_terms(preds, target, mask=mask) if a.loss == "device" else torch_terms(torch, preds, target[:, 0], mask)
         loss = val_loss.combine(terms, (1,) * a.stages)
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -184,8 +271,11 @@ def main(argv=None):
     losses = [float(v) for v in losses]
     if a.save:
         torch.save({"weights": {k: v.detach().cpu() for k, v in net.state_dict().items()}}, a.save)
-    print(json.dumps({"losses": losses, "loss_first": losses[0], "loss_last": losses[-1], "grad_norm_first": float(grad_norm_first),
-                      "seconds": dt, "loss": a.loss, "train": a.train, "images_per_step": B, "steps": a.steps, "stages": a.stages, "lr": a.lr}))
+    result = {"losses": losses, "loss_first": losses[0], "loss_last": losses[-1], "grad_norm_first": float(grad_norm_first),
+              "seconds": dt, "loss": a.loss, "train": a.train, "images_per_step": B, "steps": a.steps, "stages": a.stages, "lr": a.lr}
+    if a.augment:
+        result["augment"] = True
+    print(json.dumps(result))
     return 0
 
 

@@ -510,6 +510,44 @@ PP_API int pp_focal_l2_grad(const void *const *pred_dev, int pred_dtype, int pre
                             const int *hs, const int *ws, double multi_task_weight, double keypoint_task_weight, int flags,
                             const double *term_weight_dev, void *const *grad_dev, void *stream);
 
+/* The reference's training-data transformer (py_cocodata_server/py_data_transformer.py:42-88, :111-183, py_data_iterator.py:54-74,
+ * py_data_heatmapper.py:79-86) as one device stage: the uint8 image and both uint8 masks of every image of a batch warped with the
+ * image's own affine matrix (cv2.warpAffine INTER_LINEAR, BORDER_CONSTANT, 8-bit fixed-point path), the masks reduced to stride 4
+ * (INTER_AREA), the all-person mask eroded 3 x 3 into the foreground plane, and the joints mapped through the same matrix with the
+ * left / right exchange after a flip.  The arithmetic is the contract of INTEGRATION section 17 (csrc/posepaf_augment.hip restates
+ * it; tests/augment_reference.py is its NumPy form): it follows OpenCV 3.4, but OpenCV was not run against it.  Needs no context.
+ *   images_u8      DEVICE uint8 (batch, slot_h, slot_w, 3), image b in the top-left (h_b, w_b) corner of its slot; the rest of a
+ *                  slot is never read
+ *   sizes_dev      DEVICE int[2][batch], heights then widths (the layout of pp_preprocess_u8_ragged), clamped to the slot; NULL =
+ *                  every image fills its slot
+ *   mask_miss_u8, mask_all_u8   DEVICE uint8 (batch, slot_h, slot_w), either may be NULL: constant 255 / constant 0
+ *   m_inv_dev      DEVICE double[batch][6], the matrix as cv2.warpAffine inverts it (posepaf/rotation.py invert_affine): destination
+ *                  (x, y) reads source (m0 x + m1 y + m2, m3 x + m4 y + m5).  The fixed-point coordinates are int32: the caller keeps
+ *                  (|m0| out_w + |m1| out_h + |m2| + 1) 1024 and the same of the second row below 2^31 (posepaf/augment.py refuses
+ *                  what is beyond); beyond it pixels are wrong, but no address leaves the slot
+ *   m_fwd_dev      DEVICE double[batch][6], the forward matrix, for the joints;  flip_dev: DEVICE int[batch]
+ *   joints_in_dev  DEVICE double[batch][max_people][18][3];  n_people_dev: DEVICE int[batch], clamped to [0, max_people]
+ *   out_h, out_w   the output size, both multiples of 4;  border: HOST unsigned char[3], the image's border value
+ *   image_out      DEVICE (batch, out_h, out_w, 3), PP_F32 or PP_F16, 16-byte aligned: float(u8) / 255.0f correctly rounded (and that
+ *                  rounded to binary16)
+ *   mask_miss_out  DEVICE float (batch, out_h / 4, out_w / 4): the mask pp_focal_l2_terms takes
+ *   fg_out         DEVICE, PP_F16 or PP_F32: plane b (out_h / 4 x out_w / 4) at element b * fg_image_stride -- with the pointer at
+ *                  channel 48 of a (batch, n, 50, h, w) target and the stride n * 50 * h * w the plane lands in place
+ *   joints_out     DEVICE float[batch][max_people][18][3], the layout pp_render_scenes reads; persons at or beyond n_people[b] are
+ *                  written as they were (rounded to float32)
+ * Every output word is stored plainly on every launch; an image's outputs do not depend on the batch, the slot or the launch
+ * geometry.  PP_ERR_BAD_ARG: a null pointer (but sizes_dev and the two masks), a non-positive batch / slot / max_people / output
+ * size, out_h or out_w no multiple of 4, a dtype that is neither PP_F16 nor PP_F32, fg_image_stride below one plane, image_out off
+ * a 16-byte boundary or another pointer off its element's.  PP_ERR_UNSUPPORTED: max_people above PP_SCENE_MAX_PEOPLE.
+ * PP_ERR_TOO_LARGE: batch above 65535, a slot or output side above 32768.  PP_ERR_NO_DEVICE without a HIP device (after the argument
+ * checks).  Nothing is launched on a refusal.  Asynchronous, nothing allocated, every per-image parameter read on the device:
+ * capturable, and a captured graph replays with new draws. */
+PP_API int pp_augment_batch(const void *images_u8, const int *sizes_dev, const void *mask_miss_u8, const void *mask_all_u8, int batch,
+                            int slot_h, int slot_w, const double *m_inv_dev, const double *m_fwd_dev, const int *flip_dev,
+                            const double *joints_in_dev, const int *n_people_dev, int max_people, int out_h, int out_w,
+                            const unsigned char *border, void *image_out, int image_dtype, float *mask_miss_out, void *fg_out,
+                            int fg_dtype, long long fg_image_stride, float *joints_out, void *stream);
+
 /* A2 standalone: the arrays predict_refactor returns (utils/parse_skeletons.py:82-103).  net_out_dev as for
  * pp_process_batch; heat_hwc_dev: DEVICE float[batch][h][w][20], paf_hwc_dev: DEVICE float[batch][h][w][30]. */
 PP_API int pp_flip_average(const void *net_out_dev, int dtype, int batch, int h, int w, int flip, float *heat_hwc_dev,
