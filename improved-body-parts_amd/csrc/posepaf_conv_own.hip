@@ -87,14 +87,15 @@ typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
 // sums_row (SUMS): where this wave's partial channel sums go (float[K] of its (image, tile, pixel wave)): the binary16 outputs are
 // summed in fp32 over the wave's pixels -- per lane over its pixel tiles, then over the 16 lanes that hold the same channels.
-template <int MODE, int PT, int CT, bool SUMS = false, typename PixelOf>
+// CTU: the channel tiles of acc that hold results (the first CTU of CT; fewer than CT only in the halo kernel's half tiles)
+template <int MODE, int PT, int CT, bool SUMS = false, int CTU = CT, typename PixelOf>
 __device__ __forceinline__ void epilogue_body(const float4_t (&acc)[PT][CT], const ConvParams &p, int lane, int nbase,
                                               PixelOf pixel_of, bool do_store, float *sums_row = nullptr) {
-    static_assert(CT % 2 == 0, "channel tiles are finished in pairs");
+    static_assert(CT % 2 == 0 && CTU % 2 == 0 && CTU <= CT, "channel tiles are finished in pairs");
     const int g = lane >> 4, odd = g & 1, cbase = (g & ~1) * 4;
     const float2_t slope2 = float2_t{p.slope, p.slope};
 #pragma unroll
-    for (int jp = 0; jp < CT; jp += 2) {
+    for (int jp = 0; jp < CTU; jp += 2) {
         float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         const int co = nbase + (jp + odd) * 16 + cbase;
         const half8_t bv = *reinterpret_cast<const half8_t *>(p.bias + co);
@@ -225,7 +226,7 @@ __device__ __forceinline__ void epilogue_preloaded(const float4_t (&acc)[PT][CT]
                         out2[2 * e + 1] = (_Float16)((float)out[2 * e + 1] + (float)ev2[2 * e + 1]);
                     }
                 }
-                *reinterpret_cast<half8_t *>(p.y + (m * p.ldy + co)) = out;
+                if (!POOL || p.y) *reinterpret_cast<half8_t *>(p.y + (m * p.ldy + co)) = out;   // (y == NULL: only the pooled output is wanted)
                 if (MODE == 4 || MODE == 5) *reinterpret_cast<half8_t *>(p.y2 + (m * p.K + co)) = out2;
                 keep[i] = (MODE == 4 || MODE == 5) ? out2 : out;
             }
@@ -242,17 +243,17 @@ __device__ __forceinline__ void epilogue_preloaded(const float4_t (&acc)[PT][CT]
     }
 }
 
-template <int PT, int CT, typename PixelOf>
+template <int PT, int CT, int CTU = CT, typename PixelOf>
 __device__ __forceinline__ void epilogue_store(const float4_t (&acc)[PT][CT], const ConvParams &p, int lane, int nbase,
                                                PixelOf pixel_of, bool do_store, float *sums_row = nullptr) {
     if (nbase >= p.K) return;   // a wave whose 64 channels lie past C_out (halo kernel, C_out = 64 mod 128): wave-uniform
     // the residual mode is wave-uniform: three bodies, one scalar branch, no per-element selects
-    if (sums_row) epilogue_body<0, PT, CT, true>(acc, p, lane, nbase, pixel_of, do_store, sums_row);   // mode 0 only (launcher)
-    else if (p.mode == 0) epilogue_body<0, PT, CT>(acc, p, lane, nbase, pixel_of, do_store);
-    else if (p.mode == 1) epilogue_body<1, PT, CT>(acc, p, lane, nbase, pixel_of, do_store);
-    else if (p.mode == 2) epilogue_body<2, PT, CT>(acc, p, lane, nbase, pixel_of, do_store);
-    else if (p.mode == 3) epilogue_body<3, PT, CT>(acc, p, lane, nbase, pixel_of, do_store);
-    else epilogue_body<4, PT, CT>(acc, p, lane, nbase, pixel_of, do_store);
+    if (sums_row) epilogue_body<0, PT, CT, true, CTU>(acc, p, lane, nbase, pixel_of, do_store, sums_row);   // mode 0 only (launcher)
+    else if (p.mode == 0) epilogue_body<0, PT, CT, false, CTU>(acc, p, lane, nbase, pixel_of, do_store);
+    else if (p.mode == 1) epilogue_body<1, PT, CT, false, CTU>(acc, p, lane, nbase, pixel_of, do_store);
+    else if (p.mode == 2) epilogue_body<2, PT, CT, false, CTU>(acc, p, lane, nbase, pixel_of, do_store);
+    else if (p.mode == 3) epilogue_body<3, PT, CT, false, CTU>(acc, p, lane, nbase, pixel_of, do_store);
+    else epilogue_body<4, PT, CT, false, CTU>(acc, p, lane, nbase, pixel_of, do_store);
 }
 
 // DIAGNOSTIC (MASK bit 64 of k_conv3x3_halo): the epilogue's arithmetic and store COUNT with every store instruction covering
@@ -285,6 +286,16 @@ __device__ __forceinline__ void wait_lgkmcnt() {
 // Hand-placed matrix instruction and LDS fragment read (see k_conv3x3_halo): the accumulator is tied to its registers.
 __device__ __forceinline__ void mfma_acc(float4_t &c, const half8_t &a, const half8_t &b) {
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
+}
+// Two of them behind ONE scalar branch inside the statement: skipped when `skip` (wave-uniform) is set.  For the compiler the
+// statement is straight-line code that updates both accumulators either way -- a branch in the source would make every accumulator
+// a value merged from two paths, and the register allocator then kept both (116 registers spilled; a scratch reload counts in
+// vmcnt like the LDS-DMA, see k_conv3x3_halo).
+__device__ __forceinline__ void mfma_pair_unless(float4_t &c0, float4_t &c1, const half8_t &a0, const half8_t &a1, const half8_t &b, int skip) {
+    asm volatile("s_cmp_lg_u32 %5, 0\n\ts_cbranch_scc1 .Lpp_skip%=\n\tv_mfma_f32_16x16x32_f16 %0, %2, %4, %0\n\tv_mfma_f32_16x16x32_f16 %1, %3, %4, %1\n.Lpp_skip%=:"
+                 : "+v"(c0), "+v"(c1)
+                 : "v"(a0), "v"(a1), "v"(b), "s"(skip)
+                 : "scc");
 }
 template <int OFF>
 __device__ __forceinline__ void lds_read16(half8_t &dst, unsigned lds_addr) {
@@ -458,6 +469,14 @@ constexpr int TP = 512;  // output pixels per workgroup
 // one is a PRODUCT bit: the epilogue class "residual before the activation, with the channel sums" (pp_conv_own_res_sums_f16).
 constexpr int HALO_RES_SUMS = 2048;
 constexpr int HALO_DBG_BITS = HALO_RES_SUMS - 1;
+// Another PRODUCT bit: the half-empty last channel tile of C_out = 64 mod 128 on all four SIMDs (bn = 576 of pp_conv_own_f16).  In
+// such a tile only weight sub-tiles 0..3 hold channels, and the wn = 1 waves of the plain instance multiply zero rows through both
+// halves of every phase.  Here both channel waves of a pixel wave take TWO of the four real sub-tiles (wn * 2 + {0, 1}: 32 channels
+// for the same 128 pixels), the sixteen MFMAs of half B are not issued, and the epilogue finishes two channel tiles at
+// c_n0 + wn * 32 (the skip is a scalar branch INSIDE the statement that holds a pixel tile's two MFMAs: mfma_pair_unless).  DMA schedule, waits, fragment reads (wf[2], wf[3] and the half-B refills included), barriers and weight ring
+// are the plain instance's; every output keeps its accumulation order (channel blocks, then taps): bit-equal results.  Full tiles
+// of the same launch (C_out = 192: one full, one half) run as in the plain instance -- the flag is per tile and wave-uniform.
+constexpr int HALO_HALF = 4096;
 
 struct HaloParams {
     int TW, TH, lgTW;       // tile width (power of two, <= 128), height = 512 / TW
@@ -631,7 +650,7 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
                     (lane >> 4) * 16;
     // LDS byte addresses (32-bit) of the two halo buffers and the weight ring, for the hand-placed ds_read_b128 below
     const unsigned lds_halo = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)s_halo;
-    const unsigned lds_w = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)s_w + wn * 4 * SUB;
+    const unsigned lds_w_full = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)s_w + wn * 4 * SUB;
     unsigned R[4][2];
     auto set_R = [&]() {   // for halo buffer 0
 #pragma unroll
@@ -681,6 +700,10 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
     stage_first();
   while (true) {
     const int c_img = n_img, c_ty0 = ty0, c_tx0 = tx0, c_n0 = n0, c_tile = t_idx;   // the tile being COMPUTED
+    // HALO_HALF: this tile holds 64 channels only (wave-uniform) -- the wave's weight fragments start at sub-tile wn * 2 instead of wn * 4
+    const int half_s = (MASK & HALO_HALF) ? __builtin_amdgcn_readfirstlane(c_n0 + 64 >= p.K ? 1 : 0) : 0;   // (a scalar register: mfma_pair_unless)
+    const bool half = half_s != 0;
+    const unsigned lds_w = half ? lds_w_full - wn * 2 * SUB : lds_w_full;
     float4_t acc[PT][CT];
 #pragma unroll
     for (int i = 0; i < PT; i++)
@@ -805,8 +828,11 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
         auto tile_b = [&](auto I) {
             constexpr int i = decltype(I)::value;
             if (!(dbg & 2)) {
-                mfma_acc(acc[i][2], wf[2], xf[i]);
-                mfma_acc(acc[i][3], wf[3], xf[i]);
+                if constexpr ((MASK & HALO_HALF) != 0) mfma_pair_unless(acc[i][2], acc[i][3], wf[2], wf[3], xf[i], half_s);
+                else {
+                    mfma_acc(acc[i][2], wf[2], xf[i]);
+                    mfma_acc(acc[i][3], wf[3], xf[i]);
+                }
             }
             if (refill) xread(std::integral_constant<int, ntap>{}, I, xf[i]);
         };
@@ -875,6 +901,11 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
                 const int q = wm * PM + i * 16 + (lane & 15);
                 return ((long)c_img * p.H + c_ty0 + (q >> LGTW)) * p.W + c_tx0 + (q & (TW - 1));
             }, true, p.csum + ((((long)c_img * hp.tiles + c_tile) * WM) / hp.gimg + wm) * p.K);
+    } else if (half) {   // (HALO_HALF; PH < 0 and D == 1: launcher) this wave's two channel tiles, at c_n0 + wn * 32
+        epilogue_store<PT, CT, 2>(acc, p, lane, c_n0 + wn * 32, [&](int i) -> long {
+            const int q = wm * PM + i * 16 + (lane & 15);
+            return ((long)c_img * p.H + c_ty0 + (q >> LGTW)) * p.W + c_tx0 + (q & (TW - 1));
+        }, true);
     } else
     epilogue_store<PT, CT>(acc, p, lane, c_n0 + wn * 64, [&](int i) -> long {
         const int q = wm * PM + i * 16 + (lane & 15);
@@ -1048,6 +1079,17 @@ int launch_halo_res_sums(const ConvParams &p, const HaloParams &g, hipStream_t s
         case 6: return launch_halo_inst<HALO_RES_SUMS, 6>(p, g, st);
         case 5: return launch_halo_inst<HALO_RES_SUMS, 5>(p, g, st);
         case 4: return launch_halo_inst<HALO_RES_SUMS, 4>(p, g, st);
+        default: return PP_ERR_UNSUPPORTED;
+    }
+}
+
+// the instances that split a half-empty channel tile over both channel waves (MASK bit HALO_HALF), one per tile width
+int launch_halo_half(const ConvParams &p, const HaloParams &g, hipStream_t st) {
+    switch (g.lgTW) {
+        case 7: return launch_halo_inst<HALO_HALF, 7>(p, g, st);
+        case 6: return launch_halo_inst<HALO_HALF, 6>(p, g, st);
+        case 5: return launch_halo_inst<HALO_HALF, 5>(p, g, st);
+        case 4: return launch_halo_inst<HALO_HALF, 4>(p, g, st);
         default: return PP_ERR_UNSUPPORTED;
     }
 }
@@ -1423,6 +1465,7 @@ PP_API int pp_pw_f16(const void *x, const void *scale, const void *w, const void
 
 // The same with the 2x2 / stride 2 max-pool of the produced tensor (y; y2 in mode 4) as one more output: pool_out DEVICE
 // (m / 4, c_out) = (n, h / 2, w / 2, c_out); width = w (pixels per row), a multiple of 32 (64 for c_in = 64), h even.
+// y may be NULL: the full-resolution tensor is then not written (a caller that reads only the pooled one), nothing else changes.
 PP_API int pp_pw_pool_f16(const void *x, const void *scale, const void *w, const void *bias, const void *extra, const void *extra2,
                           void *y, void *y2, void *pool_out, long m, int hw, int width, int c_in, int c_out, int ldy, int extra_mode,
                           float slope, void *stream) {
@@ -1433,7 +1476,7 @@ PP_API int pp_pw_pool_f16(const void *x, const void *scale, const void *w, const
 
 // [x ; x2]: y = act(W [x ; x2] + bias ...), W: (c_out, c_in + c_in2) -- e.g. a residual block's last 1x1 convolution and its 1x1 skip
 // convolution (models/layers_transposed.py:12-48: out = conv3(t) + skip(x)) as one product, the skip's output never materialised.
-// pool_out / width as pp_pw_pool_f16 (NULL / 0: none).  c_in, c_in2 multiples of 32 with a supported sum.
+// pool_out / width as pp_pw_pool_f16 (NULL / 0: none; with pool_out, y may be NULL).  c_in, c_in2 multiples of 32 with a supported sum.
 PP_API int pp_pw_cat_f16(const void *x, const void *x2, const void *w, const void *bias, const void *extra, void *y, void *pool_out, long m,
                          int hw, int width, int c_in, int c_in2, int c_out, int ldy, int extra_mode, float slope, void *stream) {
     if (!x2 || c_in <= 0 || c_in2 <= 0 || (c_in & 31) || (c_in2 & 31) || (reinterpret_cast<uintptr_t>(x2) & 15) || extra_mode > 2) return PP_ERR_BAD_ARG;
@@ -1446,7 +1489,7 @@ static int pw_run(const void *x, const void *scale, const void *w, const void *b
                   void *y2, long m, int hw, int c_in, int c_out, int ldy, int extra_mode, float slope, void *pool, int width, void *stream,
                   const void *x2, int c_in2, bool pre_form, const void *pre_add) {
     // extra_mode 5 (this kernel only): the second output y2 = y + extra2 WITHOUT a tensor added before the activation
-    if (!x || !w || !bias || !y || m <= 0 || hw <= 0 || ldy < c_out || extra_mode < 0 || extra_mode == 3 || extra_mode > 5 ||
+    if (!x || !w || !bias || (!y && !pool) || m <= 0 || hw <= 0 || ldy < c_out || extra_mode < 0 || extra_mode == 3 || extra_mode > 5 ||
         (extra_mode != 0 && extra_mode != 5) != (extra != nullptr) || (extra_mode >= 4) != (extra2 != nullptr) ||
         (extra_mode >= 4) != (y2 != nullptr))
         return PP_ERR_BAD_ARG;
@@ -1583,6 +1626,10 @@ static int conv_own_run(const void *x, const void *w, const void *bias, const vo
         ((reinterpret_cast<uintptr_t>(extra2) | reinterpret_cast<uintptr_t>(y2)) & 15))
         return PP_ERR_BAD_ARG;
     if ((upsampled_input || extra_mode == 3) && bn != 512) return PP_ERR_UNSUPPORTED;   // the 8-wave 3x3 halo kernel only
+    // bn = 576 ("512 + 64"): the halo kernel's instances for C_out = 64 mod 128 (HALO_HALF) -- the plain nine-tap form with packed
+    // pixels and at most one tensor added; every other shape or form is refused
+    if (bn == 576 && (c_out % 128 != 64 || ksize != 3 || pad != 1 || dilation != 1 || extra_mode > 2 || ldx != c_in || ldy != c_out))
+        return PP_ERR_UNSUPPORTED;
     if (upsampled_input && ((h | wd) & 1)) return PP_ERR_BAD_ARG;
     if (!pp_conv_own_supported(c_in, c_out, ksize)) return PP_ERR_UNSUPPORTED;
     if (!(slope >= 0.f && slope <= 1.f)) return PP_ERR_UNSUPPORTED;   // the epilogue's LeakyReLU is max(t, slope * t)
@@ -1591,7 +1638,7 @@ static int conv_own_run(const void *x, const void *w, const void *bias, const vo
     if (al & 15) return PP_ERR_BAD_ARG;
     const int ho = h + 2 * pad - dilation * (ksize - 1), wo = wd + 2 * pad - dilation * (ksize - 1);
     if (ho <= 0 || wo <= 0) return PP_ERR_BAD_ARG;
-    if (bn != 0 && bn != 512 && ((bn != 256 && bn != 128 && bn != 64) || c_out % bn)) return PP_ERR_UNSUPPORTED;
+    if (bn != 0 && bn != 512 && bn != 576 && ((bn != 256 && bn != 128 && bn != 64) || c_out % bn)) return PP_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     DevState *ds = dev_state();
     if (!ds) return PP_ERR_HIP;
@@ -1625,6 +1672,10 @@ static int conv_own_run(const void *x, const void *w, const void *bias, const vo
 #endif
     static const int stagger = std::getenv("POSEPAF_CONV_STAGGER") ? std::atoi(std::getenv("POSEPAF_CONV_STAGGER")) : -1;   // -1: launcher's default
     p.stagger = stagger;
+    if (bn == 576) {
+        HaloParams g;
+        return halo_geometry(p, g) ? launch_halo_half(p, g, st) : PP_ERR_UNSUPPORTED;
+    }
     if (bn == 0 || bn == 512) {   // 512: the halo-tile 3x3 kernel
         HaloParams g;
         if (halo_geometry(p, g)) return launch_halo(p, g, st);

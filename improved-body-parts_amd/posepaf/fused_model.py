@@ -9,7 +9,8 @@ per-shape timing picks; the choice table can be saved, loaded, hashed and broadc
 Only the 7x7 stride-2 stem and the 50-channel heads stay on PyTorch-ROCm (MIOpen / hipBLASLt).  Structural changes:
   * BN (eval) folded:  w' = w * g / sqrt(var + eps),  b' = beta - mean * g / sqrt(var + eps)
   * only `[-1][0]` (last stage, full-resolution scale) is produced -- the sole output the inference path reads
-    (utils/parse_skeletons.py:80); the last stage's coarse-scale feature/pred heads feed nothing and are skipped
+    (utils/parse_skeletons.py:80); the coarse-scale feature / merge / pred heads of EVERY stage feed nothing that reaches it
+    (only scale 0 is added to the next stage's input) and are skipped (USE_PRUNED_SCALES)
     (forward(all_preds=True) computes all of the reference's pred[t][s] in addition: what the validation loss scores,
     posepaf/val_loss.py)
   * LeakyReLU applied in place on the conv output
@@ -40,7 +41,9 @@ USE_FUSED_CONV = True
 # configuration ids >= 100 -> workgroup tile: 256 pixels x 256 / 128 / 64 channels (implicit GEMM), or 512 = the 3x3 halo-tile kernel
 USE_OWN_CONV = True
 TUNE_MIOPEN = os.environ.get("POSEPAF_TUNE_MIOPEN", "0") == "1"   # also time MIOpen + epilogue pass where fused kernels exist
-OWN_VARIANTS = {101: 256, 102: 128, 103: 64, 104: 512}
+# (106 -> 576: the halo-tile kernel's instances for C_out = 64 mod 128, whose half-empty last channel tile runs on all four SIMDs;
+# bit-equal to 104, refuses every other shape)
+OWN_VARIANTS = {101: 256, 102: 128, 103: 64, 104: 512, 106: 576}
 UP2_COLLAPSED_BN = (256, 128, 64, 512)   # forward_up2's choices 2..5; 512: the halo-tile kernel walking the four taps of each output phase
 PW_VARIANT = 105            # the streaming 1x1 kernel (pp_pw_f16): weights resident in LDS, pixel fragments straight from HBM
 USE_PW = True
@@ -54,6 +57,15 @@ USE_POOL_FUSION = True      # the hourglass' 2x2 max-pools leave the 1x1 kernel 
 # (the published variant, models/posenet_final.py)
 USE_RES_SUM_FUSION = True   # the SE squeeze of an hourglass output leaves the residual-mode 3x3 kernel that produces it
 USE_PRE_FUSION = True       # the compress convolution reads x * s + cache: neither SE(h) nor SE(h) + cache is written
+# Only scale 0 reaches the next stage's input (models/posenet.py:115-119: `if s == 0: x = x + cache`); the coarse scales of a stage
+# feed their own heads and the next stage's coarse scales, nothing else.  Unless every prediction is asked for (all_preds), each
+# stage computes feat / mfeat / the cache add for scale 0 only.  One exception keeps the warm-up's contract: the FIRST eager forward
+# of a model on a device input of a new shape still runs every scale, because that pass is the one that tunes the layer shapes
+# (FConv._tune never runs inside a capture) -- the choice table it leaves is complete for all_preds as well, whose captured replay
+# could otherwise only take the separate forms.  Every later forward of that shape, and every capture, is pruned; the results are
+# the same bits either way.
+USE_PRUNED_SCALES = True
+USE_POOL_ONLY = True        # res1's consumers read its pooled output only: the 1x1 kernel does not write the full-resolution tensor
 PW_TUNE_MAX_CIN = 704       # widest input the PLAIN 1x1 convolution's candidate list offers pp_pw_f16 (the 768-channel instance
                             # came with the published variant; the list a models/posenet.py network is tuned over stays as it was)
 _conv_choice: dict = {}   # shape key -> tile configuration id, or -1 = MIOpen convolution + k_bias_act pass
@@ -932,17 +944,20 @@ class FResidual(nn.Module):
         res = self.skip.conv_only(x) if self.skip is not None else x
         return self.c3(self.c2(self.c1(x)), res, out=out)
 
-    def forward_pool(self, x):
-        """-> (block output, its 2x2 max-pool): the pooled tensor leaves the block's last 1x1 convolution as a second output"""
+    def forward_pool(self, x, pooled_only: bool = False):
+        """-> (block output, its 2x2 max-pool): the pooled tensor leaves the block's last 1x1 convolution as a second output.
+        pooled_only: the caller reads the pooled tensor alone -- where the one-launch form runs, the block output is not written and
+        comes back as None (the unfused forms compute it as before)."""
         if self.skip is not None:
-            y = self._cat(x, True)
+            y = self._cat(x, True, pooled_only and USE_POOL_ONLY)
             if y is not None:
                 return y
         res = self.skip.conv_only(x) if self.skip is not None else x
         return self.c3.forward_pool(self.c2(self.c1(x)), res)
 
-    def _cat_fused(self, x, want_pool, pool_ok):
-        """_cat's one-launch form, where it applies: run() -> (y, pooled or None), or None when the kernel refuses the shape"""
+    def _cat_fused(self, x, want_pool, pool_ok, pooled_only=False):
+        """_cat's one-launch form, where it applies: run() -> (y, pooled or None), or None when the kernel refuses the shape;
+        pooled_only (with pool_ok): y is not written (pp_pw_cat_f16 with y = NULL) and comes back as None"""
         from . import _lib
         if not (USE_PW and USE_CAT_SKIP and USE_OWN_CONV and x.is_cuda and x.dtype == torch.float16):
             return None
@@ -959,7 +974,7 @@ class FResidual(nn.Module):
 
         def run():
             t = _cl(self.c2(self.c1(x)))
-            xx, y = _cl(x), self.c3._out(x, h, w)
+            xx, y = _cl(x), (None if pooled_only and pool_ok else self.c3._out(x, h, w))
             pooled = self.c3._out(x, h // 2, w // 2) if pool_ok else None
             rc = _lib.load().pp_pw_cat_f16(_ptr(t), _ptr(xx), _ptr(self._wcat), _ptr(self.c3.bias), None, _ptr(y), _ptr(pooled), n * h * w,
                                            h * w, w if pool_ok else 0, c1, c2, k, k, 0, self.c3._slope, _stream(x))
@@ -968,7 +983,7 @@ class FResidual(nn.Module):
             return y, (pooled if pool_ok else (maxpool2(y) if want_pool else None))
         return run
 
-    def _cat(self, x, want_pool):
+    def _cat(self, x, want_pool, pooled_only=False):
         """conv3(t) + skip(x) as ONE product over the concatenated channels [t ; x] (pp_pw_cat_f16) when both weight matrices fit
         the streaming kernel's LDS in one piece (otherwise the input would be read once per output-channel split and nothing is
         gained); timed once per shape against the unfused form.  -> (y, pooled or None), or None."""
@@ -977,7 +992,7 @@ class FResidual(nn.Module):
         n, _, h, w = x.shape
         # (beyond 512 input channels the kernel works on 16-pixel groups, which have no 2-row form to pool)
         pool_ok = want_pool and USE_POOL_FUSION and h % 2 == 0 and w % (64 if c1 + c2 == 64 else 32) == 0 and c1 + c2 <= 512
-        run = self._cat_fused(x, want_pool, pool_ok)
+        run = self._cat_fused(x, want_pool, pool_ok, pooled_only)
         if run is None:
             return None
         key = ("cat", n, c1, c2, h, w, k, bool(self.c3.act), pool_ok)
@@ -1121,18 +1136,33 @@ class FusedIMHN(nn.Module):
                 return FusedIMHNFinal(net)
         return cls(net)
 
+    def _prune_scales(self, imgs, all_preds) -> bool:
+        """whether this forward computes scale 0 only in the stages before the last (USE_PRUNED_SCALES).  Not the first eager forward
+        on a device input of a new shape: that pass tunes the layer shapes, the coarse ones included (see USE_PRUNED_SCALES)."""
+        if all_preds or not USE_PRUNED_SCALES:
+            return False
+        if not imgs.is_cuda or _capturing():
+            return True
+        tuned = self.__dict__.setdefault("_tuned_inputs", set())
+        key = (imgs.device, imgs.dtype, tuple(imgs.shape))
+        if key in tuned:
+            return True
+        tuned.add(key)
+        return False
+
     def forward(self, imgs, stage_preds: bool = False, all_preds: bool = False):
         """stage_preds=True (tests): -> the scale-0 prediction of EVERY stage, i.e. the reference's out[t][0] for t = 0..S-1.
         all_preds=True (the validation loss): -> the reference's pred[t][s] for every stage and all K scales, a list of lists; the
         (folded) merges drive the chain as always, the heads run in addition, the last stage's coarse scales included.  The tensors
         are the heads' own: the [:, :50] view of a 64-channel pixel-major tensor where FHead took its fast path."""
         seen = []
+        prune = self._prune_scales(imgs, all_preds)
         x = imgs.permute(0, 3, 1, 2)  # NHWC storage viewed as NCHW == channels_last: no copy
         x = self.stem(x)
         # torch.cat([x, dilation(x)]) of Backbone.forward (models/layers_transposed.py:193-195) without the copy: both halves are
         # written in place -- res2's last 1x1 into [:, :C], the last dilated convolution into [:, C:] -- and the dilated chain reads
         # the first half where it lies (kernels with pixel strides: pp_pw_f16 / pp_conv_ld_f16)
-        pooled = self.res1.forward_pool(x)[1]
+        pooled = self.res1.forward_pool(x, pooled_only=True)[1]
         if USE_SLICE_OUTPUT and pooled.is_cuda and pooled.dtype == torch.float16:
             c2 = self.res2.c3.weight.shape[0]
             cd = self.dil[-1].weight.shape[0]
@@ -1151,7 +1181,8 @@ class FusedIMHN(nn.Module):
         caches, x_pooled = None, None
         for t in range(self.S):
             last = t == self.S - 1
-            scales = range(1) if last and not all_preds else range(self.K)  # the last stage's coarse heads feed nothing
+            # the coarse scales feed only their own heads and the next stage's coarse scales (USE_PRUNED_SCALES): all_preds alone needs them
+            scales = range(1) if (last or prune) and not all_preds else range(self.K)
             hg = self.hg[t](x, None if caches is None else caches[0], x_pooled)   # scale 0 comes back with its cache added
             if caches is not None:
                 hg = [hg[0]] + [hg[s] + caches[s] for s in scales if s > 0]
@@ -1254,12 +1285,14 @@ class FusedIMHNFinal(FusedIMHN):
         (folded) merges drive the chain as always, the heads run in addition, the last stage's coarse scales included.  The tensors
         are the heads' own: the [:, :50] view of a 64-channel pixel-major tensor where FHead took its fast path."""
         seen = []
+        prune = self._prune_scales(imgs, all_preds)
         x = self.stem(imgs.permute(0, 3, 1, 2))  # NHWC storage viewed as NCHW == channels_last: no copy
-        x, x_pooled = self.res3.forward_pool(self.res2(self.res1.forward_pool(x)[1]))
+        x, x_pooled = self.res3.forward_pool(self.res2(self.res1.forward_pool(x, pooled_only=True)[1]))
         caches = None
         for t in range(self.S):
             last = t == self.S - 1
-            scales = range(1) if last and not all_preds else range(self.K)  # the last stage's coarse heads feed nothing
+            # the coarse scales feed only their own heads and the next stage's coarse scales (USE_PRUNED_SCALES): all_preds alone needs them
+            scales = range(1) if (last or prune) and not all_preds else range(self.K)
             hg = self.hg[t](x, x_pooled, scales)
             # SE(h)_s (+ cache_s) is never written: the gains and the cache enter the compress convolution's input read
             feats = [self.feat[t][s](hg[s][0], self.att[t][s].gains(hg[s][0], hg[s][1]), None if caches is None else caches[s])

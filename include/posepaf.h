@@ -246,7 +246,9 @@ PP_API int pp_conv_ld_f16(const void *x, const void *w, const void *bias, const 
 /* A1 forward: the same fused convolution as pp_conv_f16 -- identical arguments and semantics -- as a HAND-WRITTEN implicit-GEMM
  * kernel (csrc/posepaf_conv_own.hip: 256-pixel x bn-channel workgroup tiles, LDS-DMA staging, v_mfma_f32_16x16x32_f16, epilogue
  * from registers; no composable_kernel).  Needs c_in % 32 == 0 and c_out % 64 == 0 (pp_conv_own_supported).  bn = output
- * channels per workgroup: 256, 128 or 64 (must divide c_out), 0 = the largest that divides c_out. */
+ * channels per workgroup: 256, 128 or 64 (must divide c_out), 0 = the largest that divides c_out; 512 = the 3x3 halo-tile
+ * kernel; 576 = its instances for c_out = 64 mod 128 (3x3, pad = dilation = 1, packed pixels, extra_mode 0 / 1 / 2), which run the
+ * half-empty last channel tile on all four SIMDs -- bit-equal to 512, PP_ERR_UNSUPPORTED for every other shape or form. */
 PP_API int pp_conv_own_supported(int c_in, int c_out, int ksize);
 /* Diagnostics (the diagnostics build only, `make -C csrc diag`: the product library compiles no ablated instance and ignores
  * POSEPAF_CONV_DBG): after a launch of the 3x3 halo kernel with POSEPAF_CONV_DBG bit 1024 set, the median over the first nwg
@@ -307,14 +309,17 @@ PP_API int pp_pw_pre_f16(const void *x, const void *scale, const void *pre_add, 
                          int c_in, int c_out, int ldy, float slope, void *stream);
 /* The same with the 2x2 / stride-2 max-pool of the tensor it produces (y; y2 in mode 4) as one more output -- the hourglass pools
  * exactly these tensors (`low = hg[i][1](pool(x))`, models/layers_transposed.py:262-266), so its pooling passes disappear.
- * pool_out: DEVICE (n, h / 2, w / 2, c_out); width = w: a multiple of 32 (64 when c_in = 64); h even. */
+ * pool_out: DEVICE (n, h / 2, w / 2, c_out); width = w: a multiple of 32 (64 when c_in = 64); h even.  y may be NULL: the
+ * full-resolution tensor is then not written (a caller that reads only the pooled one); y = NULL without pool_out is
+ * PP_ERR_BAD_ARG. */
 PP_API int pp_pw_pool_f16(const void *x, const void *scale, const void *w, const void *bias, const void *extra, const void *extra2,
                           void *y, void *y2, void *pool_out, long m, int hw, int width, int c_in, int c_out, int ldy, int extra_mode,
                           float slope, void *stream);
 
 /* pp_pw_f16 on TWO inputs whose channels continue each other along K: y = act(W [x ; x2] + bias (+ extra)), W: (c_out, c_in + c_in2).
  * A residual block's last 1x1 convolution and its 1x1 skip convolution (models/layers_transposed.py:12-48: conv3(t) + skip(x)) are one
- * product this way; the skip's output is never written.  pool_out (NULL: none) / width as pp_pw_pool_f16. */
+ * product this way; the skip's output is never written.  pool_out (NULL: none) / width as pp_pw_pool_f16; with pool_out, y may be
+ * NULL as there. */
 PP_API int pp_pw_cat_f16(const void *x, const void *x2, const void *w, const void *bias, const void *extra, void *y, void *pool_out, long m,
                          int hw, int width, int c_in, int c_in2, int c_out, int ldy, int extra_mode, float slope, void *stream);
 
