@@ -13,6 +13,8 @@ all stored as fp16.  Epilogues (include/posepaf.h, extra_mode):
   5  y = act(conv + b),  y2 = fp16(y) + e2
 act = LeakyReLU(0.01) or none.  SE gains multiply the input in binary16 before the convolution; `cat` convolves [t ; x];
 `up2` convolves the x2 nearest upsample of x; `pool` outputs are the 2x2 max-pool of the produced tensor (y2 where it exists).
+The published variant's forms: `rmean` is mode 1 with the channel mean of y on the side; `pre` is the 1x1 convolution of
+fp16(fp16(x * scale[n]) + pre_add); an `up2` key ending in "nopost" has nothing added behind it (mode 0).
 """
 from __future__ import annotations
 
@@ -38,6 +40,16 @@ def table_entries(path: str = TABLE) -> list:
     return [(_key_from_json(k), int(v)) for k, v in json.load(open(path))["entries"]]
 
 
+OFFBENCH = os.path.join(os.path.dirname(TABLE), "conv_keys_offbench.json")
+
+
+def offbench_rows(path: str = OFFBENCH) -> tuple:
+    """the key census of the image geometries off the bench's (tools/offbench_keys.py) -> (rows [{"arch", "image": [h, w], "n"}],
+    per entry of table_entries(path) the indices of the rows that look its key up)"""
+    doc = json.load(open(path))
+    return doc["rows"], doc["lookups"]
+
+
 def key_id(key) -> str:
     return "-".join(("T" if v else "F") if isinstance(v, bool) else str(v) for v in key)
 
@@ -45,7 +57,7 @@ def key_id(key) -> str:
 @dataclass
 class Spec:
     key: tuple
-    form: str        # plain / up2 / dual / mean / pool / cat
+    form: str        # plain / up2 / dual / mean / pool / cat / rmean / pre
     n: int
     c: int           # input channels of the convolution (c1 + c2 for cat)
     h: int           # input height / width (half resolution for up2)
@@ -65,6 +77,7 @@ class Spec:
     pooled: bool = False   # the form also hands over the 2x2 max-pool (of y2 when there is one)
     has_y2: bool = False
     has_mean: bool = False
+    pre_add: bool = False  # pre: a tensor is added to the scaled input before the convolution
 
     @property
     def H(self):
@@ -88,10 +101,16 @@ def parse_key(key, n: int | None = None) -> Spec:
     if not isinstance(key[0], str):
         nn_, c, h, w, k, r, pad, dil, mode, act = key[:10]
         ldx, ldy = (key[11], key[12]) if len(key) > 10 and key[10] == "slice" else (c, k)
+        # (a "pixel stride" below the channel count is torch's stride of a size-1 width -- a 1-wide map keyed as a slice, FConv._fused;
+        # there is no next pixel in the row for it to reach: the operands are packed)
+        ldx, ldy = max(ldx, c), max(ldy, k)
         s = Spec(key, "plain", nn_, c, h, w, k, r, pad, dil, mode, act, ldx=ldx, ldy=ldy)
     elif key[0] == "up2":
-        _, nn_, c, h, w, k, post2, act = key
-        s = Spec(key, "up2", nn_, c, h, w, k, 3, 1, 1, 3 if post2 else 2, act, up=True)
+        _, nn_, c, h, w, k, post2, act = key[:8]
+        nopost = len(key) > 8 and key[8] == "nopost"
+        if len(key) > 8 + nopost or (nopost and post2):
+            raise ValueError(f"unknown layer key {key}")
+        s = Spec(key, "up2", nn_, c, h, w, k, 3, 1, 1, 0 if nopost else (3 if post2 else 2), act, up=True)
     elif key[0] == "dual":
         _, nn_, c, h, w, k, r, pad, dil, act, scaled, pool_ok = key[:12]
         nores = len(key) > 12 and key[12] == "nores"
@@ -99,6 +118,12 @@ def parse_key(key, n: int | None = None) -> Spec:
     elif key[0] == "mean":
         _, nn_, c, h, w, k, act = key
         s = Spec(key, "mean", nn_, c, h, w, k, 3, 1, 1, 0, act, has_mean=True)
+    elif key[0] == "rmean":
+        _, nn_, c, h, w, k, act = key
+        s = Spec(key, "rmean", nn_, c, h, w, k, 3, 1, 1, 1, act, has_mean=True)
+    elif key[0] == "pre":
+        _, nn_, c, h, w, k, pre_add, act = key
+        s = Spec(key, "pre", nn_, c, h, w, k, 1, 0, 1, 0, act, scaled=True, pre_add=pre_add)
     elif key[0] == "pool":
         _, nn_, c, h, w, k, res, act = key
         s = Spec(key, "pool", nn_, c, h, w, k, 1, 0, 1, 1 if res else 0, act, pooled=True)
@@ -141,16 +166,21 @@ def make_operands(spec: Spec, seed: int, device="cpu") -> dict:
         ops["e2"] = randn(s.n, s.H, s.W, s.k).permute(0, 3, 1, 2)
     if s.scaled:
         ops["scale"] = torch.rand((s.n, s.c), generator=g, device=device).half()
+    if s.pre_add:
+        ops["pre"] = randn(s.n, s.h, s.w, s.c).permute(0, 3, 1, 2)
     return ops
 
 
 def conv_input(spec: Spec, ops: dict, i0: int, i1: int) -> torch.Tensor:
-    """images i0:i1 of what the convolution reads, in fp16 (SE gains multiplied in binary16; [t ; x] for cat)"""
+    """images i0:i1 of what the convolution reads, in fp16 (SE gains multiplied in binary16, then pre_add added in binary16;
+    [t ; x] for cat)"""
     x = ops["x"][i0:i1]
     if spec.form == "cat":
         x = torch.cat([ops["t"][i0:i1], x], dim=1)
     if spec.scaled:
         x = x * ops["scale"][i0:i1, :, None, None]
+    if spec.pre_add:
+        x = x + ops["pre"][i0:i1]
     return x
 
 
@@ -230,11 +260,65 @@ def reference32(spec: Spec, ops: dict, pix=None, chunk: int | None = None) -> tu
 
 
 # ---------------------------------------------------------------- float64 at chosen pixels
+def halo_tile_width(W: int) -> int:
+    """the halo kernel's tile width for a map W wide: the widest power of two up to 128 that divides W; 0 when none >= 16 does"""
+    tw = 128
+    while tw >= 16 and W % tw:
+        tw >>= 1
+    return tw if tw >= 16 else 0
+
+
+def halo_cell(n: int, H: int, W: int, dil: int = 1, up: bool = False, csum: bool = False, mode: int = 0):
+    """halo_geometry (csrc/posepaf_conv_own.hip) replayed for a 3x3 / pad = dil convolution whose channel counts the kernel takes,
+    on an (n, H, W) OUTPUT map: (tile width, tile height, images stacked in a tile, tiles per image), or None where the launcher
+    refuses the shape.  up: the input is read at half resolution; csum: channel sums on the side (their stacked form exists for
+    the residual epilogue, mode 1, only)."""
+    if dil != 1 and (dil < 3 or dil > 5 or up or csum):
+        return None
+    tw = halo_tile_width(W)
+    if not tw:
+        return None
+    th = TILE_PIXELS // tw
+    if dil > 1:
+        if tw < 32:
+            return None
+        gimg, tiles, nhalo = 1, (W // tw) * dil * -(-(-(-H // dil)) // th), (th + 2) * (tw + 2 * dil)
+    elif H % th == 0:
+        gimg, tiles, nhalo = 1, (W // tw) * (H // th), (th + 2) * (tw + 2)
+    else:
+        if tw != W or th % H or H % (128 // tw) or n % (th // H) or (csum and mode != 1):
+            return None
+        gimg, tiles, nhalo = th // H, 1, (th // H) * (H + 2) * (tw + 2)
+    npieces = -(-nhalo // 16)
+    if not 32 <= npieces <= (56 if tw == 128 or dil > 1 else 48):
+        return None
+    return tw, th, gimg, tiles
+
+
 def tile_geometry(H: int, W: int) -> tuple:
-    """(tile height, tile width, tiles per row) of the halo kernel's rule: 512 pixels, TW = min(W, 128)"""
+    """(tile height, tile width, tiles per row) of the tiles the halo kernel cuts an H x W map into (halo_geometry, dilation 1):
+    512 pixels, TW = the widest power of two up to 128 that divides W, TH = 512 / TW when it divides H.  A map lower than that
+    tile whose whole images stack in one (TW = W, H | TH, 128 / TW | H) is one tile per image, H x W.  A map the halo kernel does
+    not take runs on kernels that do not tile the image: it is cut in bands of up to 512 pixels, min(W, 128) wide (a map narrower
+    than 16 is one band) -- the rule this module had before it followed the kernel on maps that are not square powers of two."""
+    tw = halo_tile_width(W)
+    if tw:
+        th = TILE_PIXELS // tw
+        if H % th == 0:
+            return th, tw, W // tw
+        if tw == W and th % H == 0 and H % (128 // tw) == 0:
+            return H, W, 1
     tw = min(W, 128)
     th = max(1, min(TILE_PIXELS // tw, H))
     return th, tw, -(-W // tw)
+
+
+def truth_pixels(n: int, H: int, W: int, seed: int = 0) -> torch.Tensor:
+    """the pixels the float64 truth is computed at: every pixel of every image where n * H * W <= 4096, else sample_pixels"""
+    if n * H * W > 4096:
+        return sample_pixels(n, H, W, seed)
+    i, y, x = torch.meshgrid(torch.arange(n), torch.arange(H), torch.arange(W), indexing="ij")
+    return torch.stack([i.flatten(), y.flatten(), x.flatten()], 1)
 
 
 def tile_of(H, W, y, x) -> int:
@@ -294,6 +378,8 @@ def acc64_at(spec: Spec, ops: dict, pix: torch.Tensor, drop=None) -> torch.Tenso
                 v = torch.cat([_nhwc_at(ops["t"], img, sy, sx), v], 1)
             if spec.scaled:
                 v = v * ops["scale"].cpu()[img]                          # binary16 product, as the kernel's input read
+            if spec.pre_add:
+                v = v + _nhwc_at(ops["pre"], img, sy, sx)                # binary16 sum of the rounded product
             v = v.double() * ok[:, None].double()
             if drop is not None and drop[1] == i * spec.r + j:
                 v[:, drop[0]] = 0
