@@ -331,7 +331,7 @@ class SyntheticSource:
 def run_refactored(a, src, mine, model, post, dev, rank, world):
     """Refactored path on the shared engine.  -> (device uint8 records of this rank's images in local order, seconds)"""
     from posepaf import fused_model
-    from posepaf.engine import BatchFeeder, InferenceEngine
+    from posepaf.engine import InferenceEngine, run_jobs
     B = a.batch
     shapes = [src.shape(int(i)) for i in mine]
     groups = buckets_by_padded_shape(shapes)
@@ -405,20 +405,18 @@ def run_refactored(a, src, mine, model, post, dev, rank, world):
         import torch.distributed as dist
         dist.barrier()
     t0 = time.perf_counter()
-    feeder = BatchFeeder(eng, jobs, fill, workers=workers, depth=2).start()
-    for _, plan, loc, slot in feeder:
-        rec = eng.submit(slot, plan)
-        local.index_copy_(0, torch.as_tensor(loc, dtype=torch.int64).to(dev, non_blocking=True),
-                          rec.view(plan.b, RECORD_BYTES)[: len(loc)])
-        if a.render_dir:   # the canvas is the plan's until its next submit: bring it to the host now (waits for this batch)
-            canvases = plan.canvas[: len(loc)].cpu().numpy()
-            for j, k_local in enumerate(loc):
-                h, w = shapes[k_local]
-                save_image(os.path.join(a.render_dir, "%06d.%s" % (int(mine[k_local]), a.render_format)), canvases[j, :h, :w])
-                n_rendered += 1
+
+    def save_canvases(plan, loc):   # the canvas is the plan's until its next submit: bring it to the host now (waits for this batch)
+        nonlocal n_rendered
+        canvases = plan.canvas[: len(loc)].cpu().numpy()
+        for j, k_local in enumerate(loc):
+            h, w = shapes[k_local]
+            save_image(os.path.join(a.render_dir, "%06d.%s" % (int(mine[k_local]), a.render_format)), canvases[j, :h, :w])
+            n_rendered += 1
+
+    run_jobs(eng, jobs, fill, local, workers, depth=2, on_batch=save_canvases if a.render_dir else None)
     eng.sync()
     dt = time.perf_counter() - t0
-    feeder.close()
     info = {"plans": sorted(eng.plans), "decode_threads": workers,
             "conv_table": fused_model.table_hash(), "launch": "eager" if a.no_graph else "hipGraph replay"}
     if a.render_dir:

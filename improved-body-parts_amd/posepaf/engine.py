@@ -335,3 +335,21 @@ class BatchFeeder:
 
     def close(self):
         self.pool.shutdown(wait=False)
+
+
+def run_jobs(eng: InferenceEngine, jobs, fill, out, workers: int, depth: int = 2, on_batch=None):
+    """The engine thread's loop over a job list: a BatchFeeder fills the slots, every job is submitted as its slot arrives, and
+    the records of its first len(items) images are scattered into rows `items` of `out` (device uint8 (N, RECORD_BYTES)).
+    jobs, fill: as BatchFeeder takes them, the items of a job being row indices of `out`.  on_batch(plan, items), when given,
+    runs right after a job's submit and scatter: whatever it reads of the plan (canvas, maps, records) is that job's on the
+    compute stream, and the plan's next submit overwrites it.  Enqueues only; the caller synchronises."""
+    feeder = BatchFeeder(eng, jobs, fill, workers=workers, depth=depth).start()
+    try:
+        for _, plan, loc, slot in feeder:
+            rec = eng.submit(slot, plan)
+            out.index_copy_(0, torch.as_tensor(loc, dtype=torch.int64).to(eng.dev, non_blocking=True),
+                            rec.view(plan.b, RECORD_BYTES)[: len(loc)])
+            if on_batch is not None:
+                on_batch(plan, loc)
+    finally:
+        feeder.close()
