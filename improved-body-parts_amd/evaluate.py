@@ -17,6 +17,8 @@
         GPU from its joint list inside the batch's graph (default --scenes bank: 64 host-rendered scenes, image i shows i mod 64)
     python evaluate.py --val_loss --synthetic 512 --batch 32                         # the reference's validation loss (multi-scale
         focal L2 over 4 stacks x 5 scales, models/loss_model.py) of the fused model against device-rendered targets, per stack / scale
+    python evaluate.py --val_loss --ann_file F --img_dir D --mask_miss segm          # the same, masked by the reference's mask_miss,
+        rasterised on the GPU from the annotations' polygons and crowd run-length code (pp_coco_masks_u8)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 evaluate.py --synthetic 5000 ...
 
 What is kept from the reference: the flags --run_refactor / --run_cpp (:53-54; --run_cpp selects the C++ pafprocess rules --
@@ -128,9 +130,14 @@ def parse(argv=None):
                          "models/loss_model.py:23-81, :133-161; train*.py test()) of the fused model, computed on the device "
                          "(pp_focal_l2_terms).  Per batch: pad / normalise as the refactored path does, model(x, all_preds=True), the "
                          "targets rendered on the device from the image's own joints (--synthetic: its people; --ann_file: its "
-                         "annotations) with reverse_kp and no noise, mask of ones (mask_miss needs crowd segmentations).  Takes "
+                         "annotations) with reverse_kp and no noise, mask of ones unless --mask_miss segm.  Takes "
                          "--batch, --sizes, --arch, -p; prints one JSON line.  Refuses --scales, --rotation_search, --test_cfg, "
                          "--config_file, --render_dir, --render_limbs_dir, --ap and --scenes bank")
+    ap.add_argument("--mask_miss", choices=("ones", "segm"), default="ones",
+                    help="with --val_loss --ann_file: segm masks the loss with the reference's mask_miss, rasterised on the device from "
+                         "the annotations' polygons and crowd run-length code (pp_coco_masks_u8, INTEGRATION section 19) and brought "
+                         "to stride 4 by the data transformer's 4 x 4 area rule under the identity matrix (section 17); an image with "
+                         "more than one crowd annotation is skipped and counted.  ones (default): no mask")
     ap.add_argument("--scenes", choices=("bank", "device"), default=None,
                     help="where the injected scenes (--synthetic, --inject_gt) come from.  bank: rendered on the host before the "
                          "run and kept in HBM -- 64 per bucket shape for --synthetic (image i shows scene i mod 64), one per image "
@@ -199,6 +206,11 @@ class CocoSource:
         self._shapes = [(int(images[i]["height"]), int(images[i]["width"])) for i in ids]
         keep = set(ids)
         self.gts = {i: [] for i in ids}
+        self.segm = {i: [] for i in ids}         # every person annotation in annotation order, for --mask_miss segm
+        for a in anns:
+            if a["image_id"] in keep:
+                self.segm[a["image_id"]].append({"segmentation": a.get("segmentation"), "iscrowd": int(a.get("iscrowd", 0)),
+                                                 "num_keypoints": int(a.get("num_keypoints", 0))})
         for a in anns:
             if a["image_id"] in keep and "keypoints" in a:
                 self.gts[a["image_id"]].append({"keypoints": a["keypoints"], "area": float(a["area"]), "bbox": a.get("bbox"),
@@ -638,6 +650,22 @@ def val_loss_conflicts(a):
     return [name for name, given in named if given]
 
 
+def segm_mask_stride4(anns_per_image, staged, sizes, dev):
+    """--mask_miss segm for one staged batch: the annotations' mask_miss rasterised into the batch's slots (pp_coco_masks_u8) and brought
+    to stride 4 by the data transformer under the identity matrix (pp_augment_batch: the 4 x 4 area rule of INTEGRATION section 17; the
+    padding around an image reads the border value 255).  staged: device uint8 (B, hp, wp, 3); sizes: device int32 (2, B)
+    -> float32 (B, hp / 4, wp / 4), what focal_l2_terms takes as mask"""
+    from posepaf import augment, coco_masks
+    n, hp, wp, _ = staged.shape
+    hw = sizes.cpu().numpy()
+    packed = coco_masks.to_device(coco_masks.pack_segmentations(anns_per_image, [(int(hw[0, j]), int(hw[1, j])) for j in range(n)]), dev)
+    mask_miss, _ = coco_masks.masks_device(packed, (hp, wp))
+    identity = [np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])] * n
+    params = torch.from_numpy(augment.pack_params(identity, [False] * n, hp, wp)).to(dev)
+    joints = torch.zeros((n, 1, sk.NUM_PART, 3), dtype=torch.float64, device=dev)
+    return augment.augment_device(staged, mask_miss, None, sizes, joints, torch.zeros(n, dtype=torch.int32, device=dev), params, (hp, wp))[1]
+
+
 def run_val_loss(a, src, model, dev):
     """--val_loss: every image through model(x, all_preds=True) and pp_focal_l2_terms against its own device-rendered target.
     -> the meter's summary + seconds (set-up -- tuning the layer shapes of every bucket -- excluded)"""
@@ -645,8 +673,12 @@ def run_val_loss(a, src, model, dev):
     from posepaf import _lib, synth_device, val_loss
     L = _lib.load()
     B = a.batch
-    shapes = [src.shape(i) for i in range(len(src))]
-    groups = buckets_by_padded_shape(shapes)
+    segm = getattr(a, "mask_miss", "ones") == "segm"
+    # an image with more than one crowd annotation has no mask_miss (the reference's make_mask raises): skipped and counted
+    keep = [i for i in range(len(src)) if not segm or sum(s["iscrowd"] == 1 for s in src.segm[src.image_ids[i]]) <= 1]
+    if not keep:
+        raise SystemExit("--mask_miss segm: every image has more than one crowd annotation")
+    groups = {k: [keep[m] for m in members] for k, members in buckets_by_padded_shape([src.shape(i) for i in keep]).items()}
     most = src.max_people(range(len(src)))
     if most > synth_device.MAX_PEOPLE:
         raise SystemExit(f"--val_loss renders at most {synth_device.MAX_PEOPLE} people per image, an image here has {most}")
@@ -680,15 +712,19 @@ def run_val_loss(a, src, model, dev):
                     sizes[0, j], sizes[1, j] = h, w
                     people.append(src.scene_joints(i, hp, wp))
                 joints, n_people = synth_device.pack_joints(people, most)
-                x = preprocess(torch.from_numpy(imgs).to(dev), torch.from_numpy(sizes).to(dev))
+                staged, sizes_dev = torch.from_numpy(imgs).to(dev), torch.from_numpy(sizes).to(dev)
+                x = preprocess(staged, sizes_dev)
                 preds = model(x, all_preds=True)
                 target = synth_device.render_scenes(torch.from_numpy(joints).to(dev), torch.from_numpy(n_people).to(dev), hp // 4, wp // 4,
                                                     dtype=torch.float16, flip=False, noise=0.0, reverse_kp=True)
-                meter.update(val_loss.focal_l2_terms(preds, target), n_valid=n)
+                mask = segm_mask_stride4([src.segm[src.image_ids[i]] for i in loc], staged, sizes_dev, dev) if segm else None
+                meter.update(val_loss.focal_l2_terms(preds, target, mask=mask), n_valid=n)
         torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
     out = meter.summary()
-    out.update({"seconds": dt, "mask_miss": "none", "images_per_step": B, "padded_shapes": sorted(groups)})
+    out.update({"seconds": dt, "mask_miss": "segm" if segm else "none", "images_per_step": B, "padded_shapes": sorted(groups)})
+    if segm:
+        out["images_skipped_multi_crowd"] = len(src) - len(keep)
     return out
 
 
@@ -815,6 +851,8 @@ def main(argv=None):
             raise SystemExit("--val_loss needs images with joints: --synthetic N, or --ann_file F --img_dir D")
         if a.ann_file and not a.img_dir:
             raise SystemExit("--ann_file needs --img_dir")
+    if a.mask_miss == "segm" and not (a.val_loss and a.ann_file):
+        raise SystemExit("--mask_miss segm rasterises an annotation file's segmentations for --val_loss: it needs --val_loss --ann_file F")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:   # before anything touches the GPU; children are started, never exec'd
         import socket
         import subprocess

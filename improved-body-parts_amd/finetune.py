@@ -4,6 +4,7 @@
     python finetune.py --synthetic 64 --batch 8 --sizes 128x128 --steps 20 \\
         [--stages 4] [--train all|heads] [--lr 2.5e-5] [--loss device|torch] [-p weights.pth] [--seed 0] [--save out.pth]
         [--augment [--src_sizes HxW[,HxW...]]]
+    python finetune.py --ann_file person_keypoints_train2017.json --img_dir train2017 [--limit N] --batch 8 --sizes 512x512 --steps 20 ...
 
 Per step: a batch of synthetic images (random uint8 pixels, divided by 255 on the device by pp_preprocess_u8) and their
 synth.random_people joints; the targets rendered from the joints by pp_render_scenes (one sample, no noise, reverse_kp, as
@@ -26,8 +27,18 @@ evaluate.py -p loads); val_loss.focal_l2_terms -> combine -> backward() (pp_foca
                   scale_provided that box's height over the output height.  The targets are rendered from the transformed joints
                   and channel 48 receives the eroded mask_all plane after the render (the renderer zeroes that channel)
 
+  --ann_file F --img_dir D [--limit N]   real data instead of --synthetic (implies --augment): the person annotations of the first N
+                  images that have one (all without --limit), read with `json`; the images decoded with PIL (RGB -> BGR), ragged in
+                  one slot.  posepaf/coco_masks.py restates the reference's data/coco_masks_hdf5.py on the way: training_instances
+                  picks the main persons (each is one instance: objpos and scale_provided of the main person drive the matrix, the
+                  joints of everyone with keypoints are rendered), and mask_miss / mask_all are rasterised on the device from the
+                  polygons and the crowd's run-length code (pp_coco_masks_u8) into the slots the transformer
+                  reads.  An image with more than one crowd annotation is skipped and counted, as is an instance with more people
+                  than the renderer takes.  Step k takes instances k, k + ceil(n / batch), ..., as --synthetic takes images
+
 Prints one JSON line: losses (per step), loss_first, loss_last, grad_norm_first (L2 norm of the updated parameters' gradients at
-step 0), seconds, loss, train, images_per_step (and "augment": true with --augment).  Combinations it does not support end with a message before the GPU is touched.
+step 0), seconds, loss, train, images_per_step (and "augment": true with --augment; with --ann_file also "source": "annotations",
+instances, instances_skipped, images_skipped_multi_crowd).  Combinations it does not support end with a message before the GPU is touched.
 """
 import argparse
 import ctypes as C
@@ -61,7 +72,13 @@ def parse(argv=None):
     ap.add_argument("--save", default=None, help="write {'weights': state_dict} here after the last step")
     ap.add_argument("--augment", action="store_true", help="run the device data transformer in front of every step")
     ap.add_argument("--src_sizes", default=None, help="with --augment: source sizes HxW[,HxW...] (default: --sizes)")
-    return ap.parse_args(argv)
+    ap.add_argument("--ann_file", default=None, help="COCO person_keypoints JSON with segmentations: real data (implies --augment)")
+    ap.add_argument("--img_dir", default=None, help="directory of the annotation's images")
+    ap.add_argument("--limit", type=int, default=0, help="with --ann_file: only the first N images that have a person annotation")
+    a = ap.parse_args(argv)
+    if a.ann_file:
+        a.augment = True
+    return a
 
 
 def parse_src_sizes(text):
@@ -79,8 +96,24 @@ def refusals(a):
     """what this script does not do, as messages; empty when the arguments are fine (nothing here touches the GPU)"""
     from posepaf._lib import LOSS_MAX_STACKS
     out = []
-    if a.synthetic < 1:
-        out.append("--synthetic N (N >= 1) is the only data source: the reference's HDF5 dataset reader is not part of this script")
+    if a.ann_file and a.synthetic:
+        out.append("--synthetic and --ann_file are two data sources: give one")
+    elif a.ann_file:
+        if not os.path.isfile(a.ann_file):
+            out.append(f"--ann_file {a.ann_file}: no such file")
+        if not a.img_dir:
+            out.append("--ann_file needs --img_dir")
+        elif not os.path.isdir(a.img_dir):
+            out.append(f"--img_dir {a.img_dir}: no such directory")
+        if a.src_sizes is not None:
+            out.append("--src_sizes belongs to --synthetic: with --ann_file the images have their own sizes")
+        if a.limit < 0:
+            out.append("--limit must be at least 0")
+    elif a.img_dir or a.limit:
+        out.append("--img_dir and --limit belong to --ann_file")
+    elif a.synthetic < 1:
+        out.append("a data source is needed: --synthetic N (N >= 1), or --ann_file F --img_dir D (the reference's HDF5 dataset "
+                   "reader is not part of this script)")
     if a.batch < 1 or a.steps < 1:
         out.append("--batch and --steps must be at least 1")
     sizes = a.sizes.split(",")
@@ -92,7 +125,9 @@ def refusals(a):
         out.append("--sizes takes one size: a step is one batch of equally sized images")
     elif h < 64 or w < 64 or h % 64 or w % 64:
         out.append(f"--sizes {a.sizes}: both sides must be positive multiples of 64 (the coarsest of the five scales is 1/64 of the image)")
-    if a.src_sizes is not None and not a.augment:
+    if a.ann_file:
+        pass                                                         # the sources have the images' own sizes
+    elif a.src_sizes is not None and not a.augment:
         out.append("--src_sizes belongs to --augment: without it the images have the one size of --sizes")
     elif a.augment and parse_src_sizes(a.src_sizes if a.src_sizes is not None else a.sizes) is None:
         out.append(f"--src_sizes {a.src_sizes}: a comma-separated list of HxW with both sides in 8..32768")
@@ -191,6 +226,63 @@ def augment_data(a, H, W):
     return images, mask_miss, mask_all, sizes, joints, n_people, objpos, scale_provided
 
 
+def read_bgr(path):
+    """cv2.imread(path) as evaluate.py reads it: PIL, RGB -> BGR uint8 (H, W, 3)"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))[:, :, ::-1]
+
+
+def annotation_data(a, dev):
+    """--ann_file's data, staged on the device once: the images ragged in one slot, mask_miss / mask_all rasterised into the same slots
+    by pp_coco_masks_u8, sizes (2, images); per INSTANCE (coco_masks.training_instances) its image, float64 joints, n_people, and the
+    main person's objpos and scale_provided.
+    -> (images, mask_miss, mask_all, sizes, joints, n_people, objpos, scale_provided, image_of, stats)"""
+    import torch
+    from posepaf import coco_masks, synth_device
+    doc = json.load(open(a.ann_file))
+    person = [c["id"] for c in doc.get("categories", []) if c.get("name") == "person"] or [1]
+    by_image = {}
+    for ann in doc.get("annotations", []):
+        if ann.get("category_id") in person:
+            by_image.setdefault(ann["image_id"], []).append(ann)
+    metas = {im["id"]: im for im in doc["images"]}
+    ids = sorted(by_image)
+    if a.limit:
+        ids = ids[:a.limit]
+    kept, multi_crowd = [], 0
+    for i in ids:
+        if sum(1 for ann in by_image[i] if int(ann.get("iscrowd", 0)) == 1) > 1:
+            multi_crowd += 1                 # the reference's make_mask raises on such an image
+        else:
+            kept.append(i)
+    images_meta, anns = [metas[i] for i in kept], [by_image[i] for i in kept]
+    instances, skipped = coco_masks.training_instances(images_meta, anns) if kept else ([], 0)
+    if not instances:
+        raise SystemExit(f"finetune.py: --ann_file {a.ann_file}: no training instance (a person with 5 keypoints and an area of "
+                         f"32 x 32) in {len(ids)} images")
+    hw = [(int(m["height"]), int(m["width"])) for m in images_meta]
+    try:
+        packed = coco_masks.pack_segmentations(anns, hw, names=kept)
+    except coco_masks.PosePafError as e:
+        raise SystemExit(f"finetune.py: --ann_file {a.ann_file}: {e}")
+    slot_h, slot_w = max(h for h, _ in hw), max(w for _, w in hw)
+    images = np.zeros((len(kept), slot_h, slot_w, 3), np.uint8)
+    for k, (m, (h, w)) in enumerate(zip(images_meta, hw)):
+        im = read_bgr(os.path.join(a.img_dir, m["file_name"]))
+        if im.shape[:2] != (h, w):
+            raise SystemExit(f"finetune.py: {m['file_name']}: decoded size {im.shape[:2]} != annotation {(h, w)}")
+        images[k, :h, :w] = im
+    packed = coco_masks.to_device(packed, dev)
+    mask_miss, mask_all = coco_masks.masks_device(packed, (slot_h, slot_w))
+    most = max(len(inst["joints"]) for inst in instances)
+    joints, n_people = synth_device.pack_joints([inst["joints"] for inst in instances], most,
+                                                joints_out=np.zeros((len(instances), most, 18, 3), np.float64))
+    stats = {"source": "annotations", "instances": len(instances), "instances_skipped": skipped, "images_skipped_multi_crowd": multi_crowd}
+    return (images, mask_miss, mask_all, packed["sizes"], joints, n_people, [inst["objpos"][0] for inst in instances],
+            [inst["scale_provided"][0] for inst in instances], torch.tensor([inst["image"] for inst in instances], device=dev), stats)
+
+
 def main(argv=None):
     a = parse(argv)
     bad = refusals(a)
@@ -209,6 +301,7 @@ def main(argv=None):
     L = _lib.load()
     H, W = (int(v) for v in a.sizes.lower().split("x"))
     B, N = a.batch, a.synthetic
+    image_of, stats = None, {}
     net = net.float().to(dev).eval()
     pn = net.posenet
     heads = a.train == "heads"
@@ -221,8 +314,12 @@ def main(argv=None):
     if a.augment:
         import random
         from posepaf import augment
-        images, mask_miss, mask_all, sizes, joints, n_people, objpos, scale_provided = augment_data(a, H, W)
-        mask_miss, mask_all, sizes = torch.from_numpy(mask_miss).to(dev), torch.from_numpy(mask_all).to(dev), torch.from_numpy(sizes).to(dev)
+        if a.ann_file:                                            # N counts the instances; image_of[i] is the image of instance i
+            images, mask_miss, mask_all, sizes, joints, n_people, objpos, scale_provided, image_of, stats = annotation_data(a, dev)
+            N = len(objpos)
+        else:
+            images, mask_miss, mask_all, sizes, joints, n_people, objpos, scale_provided = augment_data(a, H, W)
+            mask_miss, mask_all, sizes = torch.from_numpy(mask_miss).to(dev), torch.from_numpy(mask_all).to(dev), torch.from_numpy(sizes).to(dev)
         draw_params = augment.TransformParams(tint_prob=0.0)      # the colour distortion is out of scope: never drawn
     else:
         images = np.stack([np.frombuffer(np.random.default_rng(10_000 + 1000 * a.seed + i).bytes(H * W * 3), np.uint8).reshape(H, W, 3)
@@ -245,7 +342,8 @@ def main(argv=None):
             rng = random.Random(1_000_003 * a.seed + step)
             host_idx = [(step + i * per_pass) % N for i in range(B)]
             augs = [augment.AugmentSelection.random(draw_params, rng) for _ in range(B)]
-            x, mask, fg, moved = augment.transform_batch(images[idx], mask_miss[idx], mask_all[idx], sizes[:, idx].contiguous(), joints[idx],
+            im = idx if image_of is None else image_of[idx]
+            x, mask, fg, moved = augment.transform_batch(images[im], mask_miss[im], mask_all[im], sizes[:, im].contiguous(), joints[idx],
                                                          n_people[idx], augs, [objpos[i] for i in host_idx],
                                                          [scale_provided[i] for i in host_idx], (H, W))
             target = synth_device.render_scenes(moved, n_people[idx], H // 4, W // 4, dtype=torch.float16, flip=False, noise=0.0,
@@ -275,6 +373,7 @@ def main(argv=None):
               "seconds": dt, "loss": a.loss, "train": a.train, "images_per_step": B, "steps": a.steps, "stages": a.stages, "lr": a.lr}
     if a.augment:
         result["augment"] = True
+    result.update(stats)
     print(json.dumps(result))
     return 0
 

@@ -553,6 +553,38 @@ PP_API int pp_augment_batch(const void *images_u8, const int *sizes_dev, const v
                             const unsigned char *border, void *image_out, int image_dtype, float *mask_miss_out, void *fg_out,
                             int fg_dtype, long long fg_image_stride, float *joints_out, void *stream);
 
+/* The person masks of the reference's data/coco_masks_hdf5.py (make_mask over annToMask) from polygon vertices and at most one
+ * uncompressed crowd run-length code per image: mask_miss (0 where a person is segmented without keypoints, or the crowd lies) and
+ * mask_all (255 on every person), uint8, into the slots pp_augment_batch reads.  The arithmetic is the contract of INTEGRATION
+ * section 19 (csrc/posepaf_segm.hip restates it; tests/coco_mask_reference.py is its NumPy form): it follows the published maskApi.c,
+ * but pycocotools was not run against it.  Needs no context.
+ *   verts_dev      DEVICE double[n_verts][2], every ring's (x, y) back to back
+ *   rings_dev      DEVICE int[n_rings][4], 16-byte aligned: first vertex, vertices (>= 3), order index of the ring's annotation among
+ *                  its image's, flags (bit 0: the annotation has num_keypoints <= 0 and counts for mask_miss).  An image's rings
+ *                  are consecutive.  A ring pointing outside verts_dev is skipped
+ *   images_dev     DEVICE long long[batch][5]: first ring, rings, first entry of the crowd in runs_dev, its runs (0: no crowd), the
+ *                  crowd's order index -- rings with a smaller order index are taken out of the crowd (make_mask is order-dependent)
+ *   runs_dev       DEVICE long long[n_runs]: per crowd the running sums c_0, c_0 + c_1, ... of its counts (the last is h_b w_b); pixel
+ *                  p = x h_b + y is set iff it lies in an odd-indexed run
+ *   sizes_dev      DEVICE int[2][batch], heights then widths (the layout of pp_augment_batch), clamped to the slot; NULL = every
+ *                  image fills its slot
+ *   workspace      DEVICE, 8-byte aligned, at least pp_coco_masks_workspace_bytes(n_verts) bytes: the vertices in rleFrPoly's
+ *                  integer grid.  The boundary events are found per edge and column in closed form and never stored, so the
+ *                  size does not depend on how many there are
+ *   mask_miss_u8, mask_all_u8   DEVICE uint8 (batch, slot_h, slot_w), distinct: image b in the top-left (h_b, w_b) corner of its slot;
+ *                  the rest of a slot is never written.  An image with no ring and no crowd gets 255 / 0
+ * n_verts, n_rings and n_runs are the lengths of the arrays: everything read from the tables is clamped against them, so they may be
+ * capacities above what a batch uses, and a captured graph replays with rewritten tables.  An image's masks do not depend on the
+ * batch, the slot or the launch geometry; no atomics on mask bytes.  PP_ERR_BAD_ARG: a null pointer (but sizes_dev, and an array of
+ * length 0), a non-positive batch or slot, a negative length, the two outputs being one, a pointer off its alignment, a workspace
+ * that is too small.  PP_ERR_TOO_LARGE: batch above 65535, a slot side above 32768, more than 2^24 vertices or runs or 2^20 rings.
+ * PP_ERR_NO_DEVICE without a HIP device (after the argument checks).  Nothing is launched on a refusal.  Asynchronous, nothing
+ * allocated: capturable.  pp_coco_masks_workspace_bytes: the size, or PP_ERR_BAD_ARG / PP_ERR_TOO_LARGE (negative). */
+PP_API long long pp_coco_masks_workspace_bytes(int n_verts);
+PP_API int pp_coco_masks_u8(const double *verts_dev, int n_verts, const int *rings_dev, int n_rings, const long long *images_dev,
+                            const long long *runs_dev, int n_runs, const int *sizes_dev, int batch, int slot_h, int slot_w,
+                            void *workspace, long long workspace_bytes, void *mask_miss_u8, void *mask_all_u8, void *stream);
+
 /* A2 standalone: the arrays predict_refactor returns (utils/parse_skeletons.py:82-103).  net_out_dev as for
  * pp_process_batch; heat_hwc_dev: DEVICE float[batch][h][w][20], paf_hwc_dev: DEVICE float[batch][h][w][30]. */
 PP_API int pp_flip_average(const void *net_out_dev, int dtype, int batch, int h, int w, int flip, float *heat_hwc_dev,
