@@ -1,0 +1,317 @@
+// posepaf_headgrad.hip -- the weight and bias gradient of a 1 x 1 convolution head (c_in -> c_out <= 64, no BN, no activation) from the
+// head's binary16 pixel-major input and the binary16 gradient of its output:
+//   dw[k][c] = fl32(inv_loss_scale * sum_m g[m][k] * xs[m][c]),    db[k] = fl32(inv_loss_scale * sum_m g[m][k])
+//   xs[m][c] = x[m][c], or with SE gains  half_rn(float(x[m][c]) * float(scale[m / hw][c]))  (the product of two binary16 values is
+//   exact in float32, so that is ONE rounding of the exact product: what pp_pw_f16 multiplies and pp_channel_scale_f16 stores)
+// A reduction GEMM over the pixels; both operands are contracted along the dimension that is NOT contiguous in memory.
+//
+// k_head_wgrad: a persistent grid of min(HG_MAX_WG, chunks) workgroups of 256 threads; workgroup b takes the chunks of HG_P = 64
+// pixels b, b + grid, b + 2 grid ... in that order.  A chunk is staged pixel-major into LDS -- the x rows with the gains applied,
+// the g rows zero-filled to 64 channels (channels >= c_out are never loaded from memory: a 16-byte group that straddles c_out is
+// loaded and its padding lanes are REPLACED by zero, a group wholly behind c_out is not loaded), pixels >= m as zeros -- and read
+// back with ds_read_b64_tr_b16: lane l of a wave addresses row 8 (l / 32) + (l % 16) / 4, columns 16 ((l / 16) % 2) + 4 (l % 4) of a
+// 16-pixel x 32-channel block and receives pixels 8 (l / 32) .. + 3 of channel l % 32, a second read 4 rows further the next four:
+// the lane's share of a 32x32x16 MFMA's A (from g) and B (from x) operand, both with the pixel along K.  The reads are outside any
+// divergent control flow (EXEC all ones).  Rows are padded by 64 bytes, which puts the four rows of a block on disjoint banks.
+// The MFMA is v_mfma_f32_32x32x16_bf16, four per tile: v_mfma_f32_32x32x16_f16 aligns the products of a block to the exponent FIELDS
+// of its operands and keeps about 25 bits below that, so a binary16 subnormal operand (exponent field 2^-14, leading zeros in the
+// significand -- a few percent of a real feature map) loses up to all of its product's bits: measured 2^-18.7 relative on a
+// two-pixel head, outside the contract's exact products.  Every binary16 value is EXACTLY hi + lo with hi its float32 form cut to
+// 8 significant bits and lo the remaining <= 3 bits, both normal bfloat16 numbers, and a product of two bfloat16 values is exact
+// in float32: acc += g_hi x_hi + g_hi x_lo + g_lo x_hi + g_lo x_lo, in this order, into the same accumulator.
+// Wave w owns output rows 32 (w % 2) .. + 31 and the 32-column tiles w / 2, w / 2 + 2, ... (c_in / 64 of them: 64 accumulator
+// registers per lane at c_in = 256).  The next chunk's global loads are issued into registers before the current chunk's MFMAs.
+// The bias sums come from the same LDS image: thread (k = tid % 64, q = tid / 64) adds pixels 16 q .. 16 q + 15 of channel k in
+// order; the four quarters are added in order at the end.  Every workgroup stores its c_out x c_in + c_out float32 partials with
+// plain stores; k_head_wgrad_finish adds the workgroups' partials of one element (four interleaved runs in workgroup order, then
+// ((s0 + s1) + s2) + s3), multiplies by inv_loss_scale once and stores dw / db.  No atomics, nothing is assumed zero: the order of
+// the additions follows from (m, c_in, c_out) alone.
+#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "posepaf_internal.h"
+
+namespace {
+
+constexpr int HG_THREADS = 256;
+constexpr int HG_P = 64;              // pixels of a chunk
+constexpr int HG_MAX_WG = 256;        // one workgroup per CU of an MI355X at the most
+constexpr int HG_KP = 64;             // output channels of the tile (rows >= c_out are zero)
+constexpr int HG_PAD = 32;            // binary16 elements of padding behind an LDS row (64 bytes)
+constexpr int HG_GROW = HG_KP + HG_PAD;
+
+typedef short short4v __attribute__((__vector_size__(4 * sizeof(short))));
+typedef _Float16 half8v __attribute__((ext_vector_type(8)));
+typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
+typedef unsigned short ushort8v __attribute__((ext_vector_type(8)));
+typedef float float16v __attribute__((ext_vector_type(16)));
+
+struct alignas(16) Quad {
+    unsigned v[4];
+};
+
+struct Frag {
+    short4v lo, hi;
+};
+
+// pixels row0 .. row0 + 15 (this lane: 8 of them) of the 32 channels from col0 of an LDS image with `stride` elements per row
+__device__ __forceinline__ half8v tr_frag(const __half *img, int stride, int row0, int col0, int lane) {
+    const int i = lane & 15;
+    const __half *p = img + (row0 + 8 * (lane >> 5) + (i >> 2)) * stride + col0 + 16 * ((lane >> 4) & 1) + 4 * (i & 3);
+    Frag f;
+    f.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v *)p);
+    f.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v *)(p + 4 * stride));
+    return __builtin_bit_cast(half8v, f);
+}
+
+// v = hi + lo exactly, element by element: hi the float32 form cut to bfloat16, lo the rest (<= 3 significant bits)
+__device__ __forceinline__ void split_bf16(half8v v, bf8v &hi, bf8v &lo) {
+    ushort8v h, l;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float f = (float)v[j];
+        const unsigned top = __float_as_uint(f) & 0xffff0000u;
+        h[j] = (unsigned short)(top >> 16);
+        l[j] = (unsigned short)(__float_as_uint(f - __uint_as_float(top)) >> 16);
+    }
+    hi = __builtin_bit_cast(bf8v, h), lo = __builtin_bit_cast(bf8v, l);
+}
+
+__device__ __forceinline__ unsigned scale2(unsigned x2, unsigned s2) {
+    const __half2 x = *reinterpret_cast<const __half2 *>(&x2), s = *reinterpret_cast<const __half2 *>(&s2);
+    const __half2 r = __halves2half2(__float2half_rn(__low2float(x) * __low2float(s)), __float2half_rn(__high2float(x) * __high2float(s)));
+    return *reinterpret_cast<const unsigned *>(&r);
+}
+
+// GVEC: the rows of g are 16-byte aligned (16-byte loads); else element loads
+template <int C_IN, bool GVEC>
+__global__ __launch_bounds__(HG_THREADS) void k_head_wgrad(const __half *__restrict__ g, int ldg, const __half *__restrict__ x,
+                                                            const __half *__restrict__ scale, long long m, int hw, int c_out,
+                                                            int n_chunks, float *__restrict__ partial) {
+    constexpr int XROW = C_IN + HG_PAD;
+    constexpr int VPP = C_IN / 8;                     // 16-byte groups of an x row
+    constexpr int NV = HG_P * VPP / HG_THREADS;       // x groups of a thread and chunk
+    constexpr bool SAME = HG_THREADS % VPP == 0;      // a thread's groups all sit at one channel offset
+    constexpr int NS = SAME ? 1 : NV;
+    constexpr int NB = C_IN / 64;                     // 32-column tiles of a wave
+
+    __shared__ alignas(16) __half s_x[HG_P * XROW];
+    __shared__ alignas(16) __half s_g[HG_P * HG_GROW];
+    __shared__ float s_db[HG_THREADS];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int grid = (int)gridDim.x, wg = (int)blockIdx.x;
+
+    Quad xr[NV], sr[NS], gq[GVEC ? 2 : 1];
+    unsigned short ge[GVEC ? 1 : 16];
+
+    auto load_chunk = [&](int chunk) {
+        const long long p0 = (long long)chunk * HG_P;
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            const int v = tid + HG_THREADS * i, pix = v / VPP, cv = v - pix * VPP;
+            xr[i] = Quad{{0u, 0u, 0u, 0u}};
+            if (p0 + pix < m) xr[i] = *reinterpret_cast<const Quad *>(x + (size_t)(p0 + pix) * C_IN + cv * 8);
+        }
+        if (scale) {
+            const __half *srow = scale + (size_t)(p0 / hw) * C_IN;     // hw % 64 == 0: a chunk lies in one image
+#pragma unroll
+            for (int i = 0; i < NS; i++) {
+                const int v = tid + HG_THREADS * i;
+                sr[i] = *reinterpret_cast<const Quad *>(srow + (v % VPP) * 8);
+            }
+        }
+        if (GVEC) {
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                const int v = tid + HG_THREADS * i, pix = v >> 3, c0 = (v & 7) * 8;
+                Quad q = Quad{{0u, 0u, 0u, 0u}};
+                if (p0 + pix < m && c0 < c_out) {
+                    q = *reinterpret_cast<const Quad *>(g + (size_t)(p0 + pix) * ldg + c0);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {     // padding channels of a straddling group: replaced, never computed with
+                        if (c0 + 2 * j >= c_out) q.v[j] = 0u;
+                        else if (c0 + 2 * j + 1 >= c_out) q.v[j] &= 0xffffu;
+                    }
+                }
+                gq[i] = q;
+            }
+        } else {
+            const unsigned short *gs = reinterpret_cast<const unsigned short *>(g);
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int e = tid + HG_THREADS * i, pix = e >> 6, c = e & 63;
+                ge[i] = (p0 + pix < m && c < c_out) ? gs[(size_t)(p0 + pix) * ldg + c] : (unsigned short)0;
+            }
+        }
+    };
+
+    auto stage_chunk = [&]() {
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            const int v = tid + HG_THREADS * i, pix = v / VPP, cv = v - pix * VPP;
+            Quad q = xr[i];
+            if (scale) {
+                const Quad s = sr[SAME ? 0 : i];
+#pragma unroll
+                for (int j = 0; j < 4; j++) q.v[j] = scale2(q.v[j], s.v[j]);
+            }
+            *reinterpret_cast<Quad *>(s_x + pix * XROW + cv * 8) = q;
+        }
+        if (GVEC) {
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                const int v = tid + HG_THREADS * i;
+                *reinterpret_cast<Quad *>(s_g + (v >> 3) * HG_GROW + (v & 7) * 8) = gq[i];
+            }
+        } else {
+            unsigned short *sg = reinterpret_cast<unsigned short *>(s_g);
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int e = tid + HG_THREADS * i;
+                sg[(e >> 6) * HG_GROW + (e & 63)] = ge[i];
+            }
+        }
+    };
+
+    float16v acc[NB];
+#pragma unroll
+    for (int j = 0; j < NB; j++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[j][r] = 0.0f;
+    float dbacc = 0.0f;
+    const int row_tile = wave & 1, col_tile0 = wave >> 1;
+
+    load_chunk(wg);                                   // grid <= n_chunks: every workgroup has a first chunk
+    for (int chunk = wg; chunk < n_chunks; chunk += grid) {
+        __syncthreads();                              // the previous chunk's reads of the LDS images are done
+        stage_chunk();
+        __syncthreads();
+        if (chunk + grid < n_chunks) load_chunk(chunk + grid);
+#pragma unroll
+        for (int ks = 0; ks < HG_P / 16; ks++) {
+            bf8v a_hi, a_lo;
+            split_bf16(tr_frag(s_g, HG_GROW, 16 * ks, 32 * row_tile, lane), a_hi, a_lo);
+#pragma unroll
+            for (int j = 0; j < NB; j++) {
+                bf8v b_hi, b_lo;
+                split_bf16(tr_frag(s_x, XROW, 16 * ks, 32 * (col_tile0 + 2 * j), lane), b_hi, b_lo);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_hi, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_lo, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_hi, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_lo, acc[j], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; i++) dbacc += __half2float(s_g[(16 * wave + i) * HG_GROW + lane]);
+    }
+
+    float *out = partial + (size_t)wg * ((size_t)c_out * C_IN + c_out);
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+        const int col = 32 * (col_tile0 + 2 * j) + (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = 32 * row_tile + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (row < c_out) out[(size_t)row * C_IN + col] = acc[j][r];
+        }
+    }
+    s_db[tid] = dbacc;
+    __syncthreads();
+    if (tid < c_out) out[(size_t)c_out * C_IN + tid] = ((s_db[tid] + s_db[64 + tid]) + s_db[128 + tid]) + s_db[192 + tid];
+}
+
+// element e of (dw, db): the workgroups' partials in four interleaved runs, each in workgroup order, then the four in order
+__global__ __launch_bounds__(HG_THREADS) void k_head_wgrad_finish(const float *__restrict__ partial, int n_wg, int n_dw, int n_db,
+                                                                   float inv_loss_scale, float *__restrict__ dw, float *__restrict__ db) {
+    __shared__ float s_sum[HG_THREADS];
+    const int tid = threadIdx.x, q = tid >> 6;
+    const int e = (int)blockIdx.x * 64 + (tid & 63), n = n_dw + n_db;
+    float sum = 0.0f;
+    if (e < n)
+        for (int w = q; w < n_wg; w += 4) sum += partial[(size_t)w * n + e];
+    s_sum[tid] = sum;
+    __syncthreads();
+    if (tid < 64 && e < n) {
+        const float v = (((s_sum[tid] + s_sum[64 + tid]) + s_sum[128 + tid]) + s_sum[192 + tid]) * inv_loss_scale;
+        if (e < n_dw) dw[e] = v;
+        else db[e - n_dw] = v;
+    }
+}
+
+int device_present() {
+    static int have = -1;
+    if (have < 0) {
+        int n = 0;
+        have = (hipGetDeviceCount(&n) == hipSuccess && n > 0) ? 1 : 0;
+    }
+    return have;
+}
+
+long long n_chunks_of(long long m) { return (m + HG_P - 1) / HG_P; }
+
+int grid_of(long long m) {
+    const long long c = n_chunks_of(m);
+    return (int)(c < HG_MAX_WG ? c : HG_MAX_WG);
+}
+
+template <int C_IN>
+void launch(bool gvec, int grid, hipStream_t st, const __half *g, int ldg, const __half *x, const __half *scale, long long m, int hw,
+            int c_out, int n_chunks, float *partial) {
+    if (gvec)
+        hipLaunchKernelGGL((k_head_wgrad<C_IN, true>), dim3(grid), dim3(HG_THREADS), 0, st, g, ldg, x, scale, m, hw, c_out, n_chunks, partial);
+    else
+        hipLaunchKernelGGL((k_head_wgrad<C_IN, false>), dim3(grid), dim3(HG_THREADS), 0, st, g, ldg, x, scale, m, hw, c_out, n_chunks, partial);
+}
+
+}  // namespace
+
+extern "C" int pp_head_wgrad_supported(int c_in, int c_out) {
+    return (c_in >= 64 && c_in <= 256 && c_in % 64 == 0 && c_out >= 1 && c_out <= HG_KP) ? 1 : 0;
+}
+
+extern "C" int pp_head_wgrad_chunk_pixels(void) { return HG_P; }
+
+extern "C" int pp_head_wgrad_max_workgroups(void) { return HG_MAX_WG; }
+
+extern "C" long long pp_head_wgrad_workspace_bytes(long m, int c_in, int c_out) {
+    if (m <= 0) return PP_ERR_BAD_ARG;
+    if (!pp_head_wgrad_supported(c_in, c_out)) return PP_ERR_UNSUPPORTED;
+    if ((long long)m > 2147483647ll) return PP_ERR_TOO_LARGE;
+    return (long long)grid_of(m) * ((long long)c_out * c_in + c_out) * (long long)sizeof(float);
+}
+
+extern "C" int pp_head_wgrad_f16(const void *g, int ldg, const void *x, const void *scale, long m, int hw, int c_in, int c_out,
+                                 float inv_loss_scale, void *workspace, long long workspace_bytes, float *dw, float *db, void *stream) {
+    if (!g || !x || !dw || !db || !workspace) return PP_ERR_BAD_ARG;
+    if (m <= 0 || hw <= 0 || (scale && m % hw != 0)) return PP_ERR_BAD_ARG;
+    if (c_out > 0 && ldg < c_out) return PP_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(scale) % 16 || reinterpret_cast<uintptr_t>(g) % 2 ||
+        reinterpret_cast<uintptr_t>(dw) % 4 || reinterpret_cast<uintptr_t>(db) % 4 || reinterpret_cast<uintptr_t>(workspace) % 4)
+        return PP_ERR_BAD_ARG;
+    if (!(isfinite(inv_loss_scale) && inv_loss_scale > 0.0f)) return PP_ERR_BAD_ARG;
+    if (!pp_head_wgrad_supported(c_in, c_out) || (scale && hw % 64 != 0)) return PP_ERR_UNSUPPORTED;
+    if ((long long)m > 2147483647ll) return PP_ERR_TOO_LARGE;
+    if (workspace_bytes < pp_head_wgrad_workspace_bytes(m, c_in, c_out)) return PP_ERR_BAD_ARG;
+    if (!device_present()) return PP_ERR_NO_DEVICE;
+
+    const int n_chunks = (int)n_chunks_of(m), grid = grid_of(m);
+    const bool gvec = reinterpret_cast<uintptr_t>(g) % 16 == 0 && ldg % 8 == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const __half *gh = static_cast<const __half *>(g), *xh = static_cast<const __half *>(x), *sh = static_cast<const __half *>(scale);
+    float *partial = static_cast<float *>(workspace);
+    switch (c_in) {
+        case 64: launch<64>(gvec, grid, st, gh, ldg, xh, sh, m, hw, c_out, n_chunks, partial); break;
+        case 128: launch<128>(gvec, grid, st, gh, ldg, xh, sh, m, hw, c_out, n_chunks, partial); break;
+        case 192: launch<192>(gvec, grid, st, gh, ldg, xh, sh, m, hw, c_out, n_chunks, partial); break;
+        default: launch<256>(gvec, grid, st, gh, ldg, xh, sh, m, hw, c_out, n_chunks, partial); break;
+    }
+    if (hipGetLastError() != hipSuccess) return PP_ERR_HIP;
+    const int n_dw = c_out * c_in, n = n_dw + c_out;
+    hipLaunchKernelGGL(k_head_wgrad_finish, dim3((n + 63) / 64), dim3(HG_THREADS), 0, st, static_cast<const float *>(partial), grid, n_dw, c_out,
+                       inv_loss_scale, dw, db);
+    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
+}

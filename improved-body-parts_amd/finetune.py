@@ -4,6 +4,8 @@
     python finetune.py --synthetic 64 --batch 8 --sizes 128x128 --steps 20 \\
         [--stages 4] [--train all|heads] [--lr 2.5e-5] [--loss device|torch] [-p weights.pth] [--seed 0] [--save out.pth]
         [--augment [--src_sizes HxW[,HxW...]]]
+    python finetune.py --model fused --train heads --synthetic 64 --batch 8 --sizes 512x512 --steps 20 \\
+        [--arch posenet|final|auto] [-p weights.pth] [--stages 4] [--loss_scale auto|N] [--wgrad device|torch]
     python finetune.py --ann_file person_keypoints_train2017.json --img_dir train2017 [--limit N] --batch 8 --sizes 512x512 --steps 20 ...
 
 Per step: a batch of synthetic images (random uint8 pixels, divided by 255 on the device by pp_preprocess_u8) and their
@@ -35,6 +37,15 @@ evaluate.py -p loads); val_loss.focal_l2_terms -> combine -> backward() (pp_foca
                   polygons and the crowd's run-length code (pp_coco_masks_u8) into the slots the transformer
                   reads.  An image with more than one crowd annotation is skipped and counted, as is an instance with more people
                   than the renderer takes.  Step k takes instances k, k + ceil(n / batch), ..., as --synthetic takes images
+
+  --model fused   (needs --train heads) the fused fp16 forward (posepaf/fused_model.py, prediction-merge fold off) takes the place of
+                  the float32 module: posepaf/head_train.HeadTrainer runs the forward under no_grad, pp_focal_l2_terms /
+                  pp_focal_l2_grad with the term weights times --loss_scale, pp_head_wgrad_f16 per head and
+                  the same SGD on float32 masters of the twenty heads.  --loss_scale auto | a power of two (auto: the largest that
+                  keeps a binary16 gradient finite for predictions in [-1, 2]); --wgrad torch forms dw / db from the same captured
+                  tensors with a float64 matmul, for A/B; --arch as evaluate.py's.  The data path (--synthetic, --augment, --ann_file)
+                  is the same; --save writes {'weights': HeadTrainer.state_dict()}, which evaluate.py -p loads.  The JSON line gains
+                  "model": "fused", "wgrad", "loss_scale" and "skipped_steps" (steps whose gradient was not finite: no update)
 
 Prints one JSON line: losses (per step), loss_first, loss_last, grad_norm_first (L2 norm of the updated parameters' gradients at
 step 0), seconds, loss, train, images_per_step (and "augment": true with --augment; with --ann_file also "source": "annotations",
@@ -75,6 +86,10 @@ def parse(argv=None):
     ap.add_argument("--ann_file", default=None, help="COCO person_keypoints JSON with segmentations: real data (implies --augment)")
     ap.add_argument("--img_dir", default=None, help="directory of the annotation's images")
     ap.add_argument("--limit", type=int, default=0, help="with --ann_file: only the first N images that have a person annotation")
+    ap.add_argument("--model", choices=("plain", "fused"), default="plain", help="fused: train the heads on the fused fp16 forward")
+    ap.add_argument("--arch", choices=("posenet", "final", "auto"), default="posenet", help="with --model fused: the architecture")
+    ap.add_argument("--loss_scale", default="auto", help="with --model fused: 'auto' or a power of two")
+    ap.add_argument("--wgrad", choices=("device", "torch"), default="device", help="with --model fused: pp_head_wgrad_f16 or the torch A/B form")
     a = ap.parse_args(argv)
     if a.ann_file:
         a.augment = True
@@ -116,6 +131,16 @@ def refusals(a):
                    "reader is not part of this script)")
     if a.batch < 1 or a.steps < 1:
         out.append("--batch and --steps must be at least 1")
+    if a.model == "fused":
+        from posepaf.head_train import is_power_of_two
+        if a.train != "heads":
+            out.append("--model fused trains the heads only (the fused model has no backward): pass --train heads")
+        if a.loss != "device":
+            out.append("--model fused takes the loss gradient from pp_focal_l2_grad: --loss torch belongs to --model plain")
+        if a.loss_scale != "auto" and not is_power_of_two(a.loss_scale):
+            out.append(f"--loss_scale {a.loss_scale}: 'auto' or a power of two (2^-24 .. 2^24)")
+    elif a.arch != "posenet" or a.loss_scale != "auto" or a.wgrad != "device":
+        out.append("--arch, --loss_scale and --wgrad belong to --model fused")
     sizes = a.sizes.split(",")
     try:
         h, w = (int(v) for v in sizes[0].lower().split("x"))
@@ -291,8 +316,9 @@ def main(argv=None):
     import torch
     from posepaf import _lib, synth, synth_device, val_loss
     from posepaf.model_init import build_network
+    fused = a.model == "fused"
     try:
-        net, _ = build_network("posenet", a.checkpoint_path, 7 + a.seed, nstack=a.stages)
+        net, _ = build_network(a.arch if fused else "posenet", a.checkpoint_path, 7 + a.seed, nstack=a.stages)
     except (ValueError, KeyError, RuntimeError) as e:
         raise SystemExit(f"finetune.py: -p {a.checkpoint_path}: {e}")
     if not torch.cuda.is_available():
@@ -302,13 +328,28 @@ def main(argv=None):
     H, W = (int(v) for v in a.sizes.lower().split("x"))
     B, N = a.batch, a.synthetic
     image_of, stats = None, {}
-    net = net.float().to(dev).eval()
-    pn = net.posenet
     heads = a.train == "heads"
-    for name, p in pn.named_parameters():
-        p.requires_grad_(name.startswith("outs.") or not heads)
-    params = [p for p in pn.parameters() if p.requires_grad]
-    opt = torch.optim.SGD(params, lr=a.lr, momentum=MOMENTUM, weight_decay=WEIGHT_DECAY)
+    if fused:
+        from posepaf import head_train
+        try:
+            tr = head_train.HeadTrainer(net, dev, lr=a.lr, momentum=MOMENTUM, weight_decay=WEIGHT_DECAY, wgrad=a.wgrad,
+                                        loss_scale="auto" if a.loss_scale == "auto" else float(a.loss_scale))
+        except _lib.PosePafError as e:
+            raise SystemExit(f"finetune.py: --model fused: {e}")
+        a.stages = tr.T
+        # the per-shape kernel choices are timed on the first forward: runs that share POSEPAF_CACHE_DIR execute the same kernels
+        from posepaf import fused_model
+        fused_model.load_table()
+        # the few layer shapes no fused kernel takes (3 x 3 on a 1 x 1 map) run on MIOpen, whose default solver there does not add
+        # in a fixed order: with this flag a step is the same bits from run to run
+        torch.backends.cudnn.deterministic = True
+    else:
+        net = net.float().to(dev).eval()
+        pn = net.posenet
+        for name, p in pn.named_parameters():
+            p.requires_grad_(name.startswith("outs.") or not heads)
+        params = [p for p in pn.parameters() if p.requires_grad]
+        opt = torch.optim.SGD(params, lr=a.lr, momentum=MOMENTUM, weight_decay=WEIGHT_DECAY)
 
     # the data: N images and their people, staged on the device once
     if a.augment:
@@ -355,6 +396,11 @@ def main(argv=None):
                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
             target = synth_device.render_scenes(joints[idx], n_people[idx], H // 4, W // 4, dtype=torch.float16, flip=False, noise=0.0,
                                                 reverse_kp=True)
+        if fused:
+            losses.append(tr.step(x, target, mask))
+            if step == 0:
+                grad_norm_first = tr.grad_norm()
+            continue
         preds = forward(pn, x, heads)
         terms = val_loss.focal_l2_terms(preds, target, mask=mask) if a.loss == "device" else torch_terms(torch, preds, target[:, 0], mask)
         loss = val_loss.combine(terms, (1,) * a.stages)
@@ -367,10 +413,14 @@ def main(argv=None):
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     losses = [float(v) for v in losses]
+    if fused:
+        fused_model.save_table()
     if a.save:
-        torch.save({"weights": {k: v.detach().cpu() for k, v in net.state_dict().items()}}, a.save)
+        torch.save({"weights": {k: v.detach().cpu() for k, v in (tr if fused else net).state_dict().items()}}, a.save)
     result = {"losses": losses, "loss_first": losses[0], "loss_last": losses[-1], "grad_norm_first": float(grad_norm_first),
               "seconds": dt, "loss": a.loss, "train": a.train, "images_per_step": B, "steps": a.steps, "stages": a.stages, "lr": a.lr}
+    if fused:
+        result.update({"model": "fused", "wgrad": a.wgrad, "loss_scale": tr.loss_scale_for(B), "skipped_steps": int(tr.skipped_steps)})
     if a.augment:
         result["augment"] = True
     result.update(stats)

@@ -46,6 +46,8 @@ EXPORTS = [
     "pp_draw_limbs_u8", "pp_limb_angle_table", "pp_limb_angle_deg",
     "pp_coco_rows_f32", "pp_oks_match", "pp_render_scenes", "pp_focal_l2_workspace_bytes", "pp_focal_l2_terms",
     "pp_focal_l2_grad", "pp_augment_batch", "pp_coco_masks_workspace_bytes", "pp_coco_masks_u8",
+    "pp_head_wgrad_supported", "pp_head_wgrad_chunk_pixels", "pp_head_wgrad_max_workgroups", "pp_head_wgrad_workspace_bytes",
+    "pp_head_wgrad_f16",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -138,6 +140,12 @@ def load():
     L.pp_coco_masks_workspace_bytes.argtypes = [C.c_int]
     L.pp_coco_masks_workspace_bytes.restype = C.c_longlong
     L.pp_coco_masks_u8.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, vp]
+    L.pp_head_wgrad_supported.argtypes = [C.c_int, C.c_int]
+    L.pp_head_wgrad_chunk_pixels.argtypes = []
+    L.pp_head_wgrad_max_workgroups.argtypes = []
+    L.pp_head_wgrad_workspace_bytes.argtypes = [C.c_long, C.c_int, C.c_int]
+    L.pp_head_wgrad_workspace_bytes.restype = C.c_longlong
+    L.pp_head_wgrad_f16.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_longlong, vp, vp, vp]
     L.pp_flip_average.argtypes =[vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_pwconv_supported.argtypes = [C.c_int, C.c_int]
     L.pp_pwconv_f16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int, vp]

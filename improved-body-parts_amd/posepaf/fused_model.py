@@ -1088,7 +1088,9 @@ class FFeature(nn.Module):
 class FusedIMHN(nn.Module):
     """forward(NHWC image batch in [0,1]) -> (N, 50, H/4, W/4): the `[-1][0]` output of NetworkEval."""
 
-    def __init__(self, net):
+    def __init__(self, net, folded_merge=None):
+        """folded_merge: None takes the module flag USE_FOLDED_MERGE; False keeps the heads and the prediction-merge convolutions in
+        the chain (a head's new weights then reach the next stage with no re-fold: posepaf/head_train.py)"""
         super().__init__()
         p = net.posenet
         self.S, self.K = p.num_stages, p.num_scales
@@ -1098,15 +1100,15 @@ class FusedIMHN(nn.Module):
         self.dil = nn.ModuleList([_fconv_from_block(d) for d in pre.dilation])
         self.hg = nn.ModuleList([FHourglass(h) for h in p.hourglass])
         self.feat = nn.ModuleList([nn.ModuleList([FFeature(s) for s in f.before_regress]) for f in p.features])
-        self._init_heads_and_merges(p)
+        self._init_heads_and_merges(p, folded_merge)
 
-    def _init_heads_and_merges(self, p):
+    def _init_heads_and_merges(self, p, folded_merge=None):
         """outs / merge_features / merge_preds: the same modules in both architectures (models/posenet.py, models/posenet_final.py)"""
         self.head = nn.ModuleList([nn.ModuleList([FHead(c.conv, c.bn, c.relu is not None) for c in o]) for o in p.outs])
         self.mfeat = nn.ModuleList([nn.ModuleList([_fconv_from_block(m.conv) for m in ms]) for ms in p.merge_features])
         self.mpred = nn.ModuleList([nn.ModuleList([_fconv_from_block(m.conv) for m in ms]) for ms in p.merge_preds])
         # cache_s = merge_pred(pred) + merge_feat(feat): both are bias-only 1x1 convs -> one epilogue with the summed bias
-        self.folded_merge = bool(USE_FOLDED_MERGE)
+        self.folded_merge = bool(USE_FOLDED_MERGE if folded_merge is None else folded_merge)
         for t_, (mf, mp) in enumerate(zip(self.mfeat, self.mpred)):
             for s_, (f, q) in enumerate(zip(mf, mp)):
                 f.bias = nn.Parameter(f.bias + q.bias, requires_grad=False)
@@ -1128,13 +1130,13 @@ class FusedIMHN(nn.Module):
                 q.w_in64 = nn.Parameter(wq, requires_grad=False)
 
     @classmethod
-    def from_network(cls, net):
+    def from_network(cls, net, folded_merge=None):
         """the fused form of a NetworkEval: FusedIMHN for models/posenet.py, FusedIMHNFinal for models/posenet_final.py"""
         if cls is FusedIMHN:
             from models import posenet_final
             if isinstance(net.posenet, posenet_final.PoseNet):
-                return FusedIMHNFinal(net)
-        return cls(net)
+                return FusedIMHNFinal(net, folded_merge)
+        return cls(net, folded_merge)
 
     def _prune_scales(self, imgs, all_preds) -> bool:
         """whether this forward computes scale 0 only in the stages before the last (USE_PRUNED_SCALES).  Not the first eager forward
@@ -1267,7 +1269,7 @@ class FusedIMHNFinal(FusedIMHN):
     (N, 50, H/4, W/4), the `[-1][0]` output of its NetworkEval.  Heads, merges and the folded merge are FusedIMHN's (the reference's
     two files agree on them); backbone, hourglass, SE placement and before_regress are this variant's."""
 
-    def __init__(self, net):
+    def __init__(self, net, folded_merge=None):
         nn.Module.__init__(self)
         p = net.posenet
         self.S, self.K = p.nstack, 5
@@ -1277,7 +1279,7 @@ class FusedIMHNFinal(FusedIMHN):
         self.hg = nn.ModuleList([FHourglassFinal(h) for h in p.hourglass])
         self.att = nn.ModuleList([nn.ModuleList([FSE(se) for se in ses]) for ses in p.channel_attention])
         self.feat = nn.ModuleList([nn.ModuleList([FFeatureFinal(s) for s in f.before_regress]) for f in p.features])
-        self._init_heads_and_merges(p)
+        self._init_heads_and_merges(p, folded_merge)
 
     def forward(self, imgs, stage_preds: bool = False, all_preds: bool = False):
         """stage_preds=True (tests): -> the scale-0 prediction of EVERY stage, i.e. the reference's out[t][0] for t = 0..S-1.

@@ -727,6 +727,31 @@ PP_API int pp_default_test_cfg(pp_test_cfg *cfg);
 PP_API int pp_set_test_cfg(pp_ctx *ctx, const pp_test_cfg *cfg);
 PP_API int pp_get_test_cfg(const pp_ctx *ctx, pp_test_cfg *cfg);
 
+/* ---------------------------------------------------------------- 1 x 1 head: weight and bias gradient (training the heads)
+ * dw[k][c] = fl32(inv_loss_scale * A[k][c]), A[k][c] the float32 accumulation over all m of the exact products g[m][k] * xs[m][c];
+ * db[k] = fl32(inv_loss_scale * sum_m g[m][k]).  xs[m][c] = x[m][c] when scale is NULL, else the binary16 rounding (nearest even,
+ * one rounding) of the exact product x[m][c] * scale[m / hw][c]: what pp_pw_f16 multiplies and pp_channel_scale_f16 stores.
+ *   g      DEVICE binary16 (m, ldg): channels 0 .. c_out - 1 of a pixel are read, the rest never enter arithmetic; 16-byte loads
+ *          where the rows are 16-byte aligned (g on a 16-byte boundary and ldg % 8 == 0), element loads elsewhere
+ *   x      DEVICE binary16 (m, c_in), packed pixel-major (NHWC);  scale  DEVICE binary16 (m / hw, c_in) or NULL
+ *   dw     DEVICE float32 (c_out, c_in);  db  DEVICE float32 (c_out): every element is stored on every call, nothing else is
+ * Two plain launches on `stream`: per-workgroup partials into the workspace (never assumed zero, never needs clearing), then a
+ * reduction in a fixed order that multiplies by inv_loss_scale once.  No floating-point atomics: the order of the float32 additions
+ * follows from (m, c_in, c_out) alone, so the result is bit-equal from run to run, eager or replayed from a graph, at every pointer
+ * alignment the entry accepts.  Asynchronous, allocates nothing, needs no pp_ctx, capturable.
+ * Refusals (nothing launched, outputs untouched), in this order:  PP_ERR_BAD_ARG: a null g, x, dw, db or workspace; m <= 0, hw <= 0,
+ * m % hw != 0 with a scale; ldg < c_out; x or scale off a 16-byte boundary, g off a 2-byte one, dw, db or the workspace off a 4-byte
+ * one; inv_loss_scale not finite and positive.  PP_ERR_UNSUPPORTED: pp_head_wgrad_supported is 0, or a scale with hw % 64 != 0 (the
+ * forward's rule: materialise and pass NULL).  PP_ERR_TOO_LARGE: m > 2^31 - 1.  PP_ERR_BAD_ARG: a workspace smaller than
+ * pp_head_wgrad_workspace_bytes.  PP_ERR_NO_DEVICE after those. */
+PP_API int pp_head_wgrad_supported(int c_in, int c_out);   /* c_in % 64 == 0, 64..256; c_out 1..64 */
+PP_API int pp_head_wgrad_chunk_pixels(void);               /* pixels one workgroup contracts per pass */
+PP_API int pp_head_wgrad_max_workgroups(void);             /* upper bound of the first launch's grid */
+/* bytes, or a negative pp_status for arguments pp_head_wgrad_f16 refuses */
+PP_API long long pp_head_wgrad_workspace_bytes(long m, int c_in, int c_out);
+PP_API int pp_head_wgrad_f16(const void *g, int ldg, const void *x, const void *scale, long m, int hw, int c_in, int c_out,
+                             float inv_loss_scale, void *workspace, long long workspace_bytes, float *dw, float *db, void *stream);
+
 /* ---------------------------------------------------------------- Python twins, host form
  * utils.parse_skeletons.find_connections / find_humans (:324-600) with host arrays, for callers of the non --run_cpp
  * branch of evaluate.py (:88-89).  peaks: joint-list rows [x, y, score, id, part] (n of them); paf: (H, W, C) float32.
