@@ -15,6 +15,15 @@ act = LeakyReLU(0.01) or none.  SE gains multiply the input in binary16 before t
 `up2` convolves the x2 nearest upsample of x; `pool` outputs are the 2x2 max-pool of the produced tensor (y2 where it exists).
 The published variant's forms: `rmean` is mode 1 with the channel mean of y on the side; `pre` is the 1x1 convolution of
 fp16(fp16(x * scale[n]) + pre_add); an `up2` key ending in "nopost" has nothing added behind it (mode 0).
+
+Where the roundings sit (held to the bit by tests/test_gpu_conv_exact.py on exact operands, `expected_exact` below): the
+accumulator conv + b (+ e1 in modes 1 and 4) is fp32; the activation is max(t, t * slope) with the product rounded to fp32; every
+output is rounded to binary16 once, at the store; the inner binary16 roundings are the SE product, the pre_add sum, and fp16(act) /
+fp16(y) in front of the adds of modes 3, 4, 5.  The 2x2 maximum orders -0 below +0 (IEEE 754-2019 `maximum`).  The channel mean is
+fp16(sum fp16(y) * fl32(1 / hw)): the fp32 sum of the binary16 outputs TIMES the fp32 reciprocal of the pixel count, the product
+rounded to binary16 once (multiply and conversion are one instruction) -- not sum / hw: where hw is no power of two the two differ
+at ties (sum / hw exactly between two binary16 numbers: the reciprocal's own rounding error, 2^-25 upwards for hw = 3 * 2^j,
+decides the side instead of the even mantissa; measured: 1 of 512 means of a 32 x 48 map).
 """
 from __future__ import annotations
 
@@ -448,3 +457,247 @@ def assert_close(got, ref, bound, label, pix=None, img0=0):
 
 def bound_for(ref_max: float, tol: float = TOL) -> float:
     return tol * max(1.0, float(ref_max))
+
+
+# ---------------------------------------------------------------- exact operands, exact expectations
+# Operands for which every fp32 partial sum of the convolution is exact IN ANY ORDER: the only roundings left are the ones the
+# module docstring names, the expected output is known to the last bit, and a kernel is compared with it as integers
+# (tests/test_gpu_conv_exact.py; the house style of test_exact_small_integers in tests/test_gpu_head_wgrad.py).
+RECIPES = ("small", "rounding", "subnormal")
+SUBNORMAL_UNIT = 2.0 ** -24          # the binary16 subnormal grid
+EXACT_LIMIT = 2.0 ** 24              # fp32 holds every integer below it
+GAINS = (0.5, 1.0, 1.5, 2.0)
+
+
+def inner_roundings(spec: Spec) -> list:
+    """the binary16 roundings INSIDE the form's contract (the final store is not one): "scale" fp16(x * s), "pre"
+    fp16(fp16(x * s) + pre_add), "act" fp16(act) in front of the adds of modes 3, 4, 5"""
+    return (["scale"] if spec.scaled else []) + (["pre"] if spec.pre_add else []) + (["act"] if spec.mode in (3, 4, 5) else [])
+
+
+def recipes_for(spec: Spec) -> list:
+    """`rounding` goes to the forms with an inner rounding.  The channel-mean forms are left out of it: their sums are fp32 sums in
+    a kernel-chosen order, exact only while sum |fp16(y)| stays below 2^24 grid units, which magnitudes beyond 2048 over a map of
+    thousands of pixels do not allow (their only rounding besides the store is the mean's own, which `small` has as well)."""
+    return ["small"] + (["rounding"] if inner_roundings(spec) and not spec.has_mean else []) + ["subnormal"]
+
+
+def make_exact_operands(spec: Spec, seed: int, recipe: str, device="cpu") -> dict:
+    """make_operands' dictionary and layouts with operands on a grid (drawn by a CPU generator, then moved to `device`).
+    small      x integers in [-3, 3], weights in [-2, 2], bias / e1 / e2 / pre_add in [-8, 8], SE gains from {0.5, 1, 1.5, 2}.
+               The channel-mean forms (`mean`, `rmean`) get x and weights from {0, 1} and bias / e1 from [0, 8] instead: the
+               product's slope is 0.01, a negative output fp16(0.01 t) sits on a 2^-17 grid, and an fp32 sum of such values over a
+               map is not exact in every order; without negative outputs every y is an integer and sum y < 2^24.  (The negative
+               branch of their epilogue is reached under `subnormal`, where every binary16 value is on ONE grid.)
+    rounding   magnitudes at which the inner roundings are visible.  Scaled forms: two input channels hold odd integers of magnitude
+               1025 .. 2047 under a gain of 1.5 or 3 (the product needs more than 11 bits, as in test_exact_product_needs_its_rounding
+               of tests/test_gpu_head_wgrad.py), so accumulators reach +-25000 and fp16(y) + e2 differs from y + e2.  Unscaled forms:
+               x integers up to +-1500 sqrt(1.5 / fan_in) (accumulators of standard deviation ~1500, many beyond 2048); e1 / e2 in
+               [-255, 255].
+    subnormal  `small` (mixed signs for every form) with x, bias, e1, e2 and pre_add multiplied by 2^-24: every input value and every
+               output is a binary16 subnormal or zero, every accumulator an integer multiple of 2^-24."""
+    assert recipe in RECIPES, recipe
+    assert recipe != "rounding" or "rounding" in recipes_for(spec), f"{spec.form}: no inner rounding to show"
+    g = torch.Generator().manual_seed(seed)
+    s, ops = spec, {}
+    nonneg = s.has_mean and recipe == "small"
+    unit = SUBNORMAL_UNIT if recipe == "subnormal" else 1.0
+    xmax, wmax, emax = (1, 1, 8) if nonneg else (3, 2, 8)
+    if recipe == "rounding":
+        emax = 255
+        if not s.scaled:
+            xmax = max(3, min(255, int(1500.0 * math.sqrt(1.5 / s.fan_in))))
+
+    def ints(lo, hi, *shape):
+        return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+    def put(t):
+        return t.half().to(device)
+
+    lo = 0 if nonneg else -1
+    if s.form == "cat":
+        xs = {"t": ints(lo * xmax, xmax, s.n, s.h, s.w, s.c1), "x": ints(lo * xmax, xmax, s.n, s.h, s.w, s.c2)}
+    else:
+        ld = s.ldx or s.c
+        xs = {"x": ints(lo * xmax, xmax, s.n, s.h, s.w, ld)}
+    if s.scaled:
+        scale = torch.tensor(GAINS)[torch.randint(0, len(GAINS), (s.n, s.c), generator=g)]
+        if recipe == "rounding":
+            big = torch.randperm(s.c, generator=g)[:2]
+            mag = 1025 + 2 * torch.randint(0, 512, (s.n, s.h, s.w, 2), generator=g)                      # odd, 1025 .. 2047
+            sign = 1 - 2 * torch.randint(0, 2, (s.n, s.h, s.w, 2), generator=g)
+            xs["x"][..., big] = (mag * sign).float()
+            scale[:, big] = torch.tensor((1.5, 3.0))[torch.randint(0, 2, (s.n, 2), generator=g)]
+        ops["scale"] = put(scale)
+    for name, v in xs.items():
+        v = put(v * unit).permute(0, 3, 1, 2)
+        ops[name] = v[:, v.shape[1] - s.c:] if name == "x" and s.form != "cat" else v
+    ops["w"] = _cl(put(ints(lo * wmax, wmax, s.k, s.c, s.r, s.r)))
+    ops["b"] = put(ints(lo * 8, 8, s.k) * unit)
+    if s.mode in (1, 2, 3, 4):
+        ops["e1"] = put(ints(lo * emax, emax, s.n, s.H, s.W, s.k) * unit).permute(0, 3, 1, 2)
+    if s.mode in (3, 4, 5):
+        ops["e2"] = put(ints(lo * emax, emax, s.n, s.H, s.W, s.k) * unit).permute(0, 3, 1, 2)
+    if s.pre_add:
+        ops["pre"] = put(ints(-8, 8, s.n, s.h, s.w, s.c) * unit).permute(0, 3, 1, 2)
+    return ops
+
+
+def _to_half_once(t64: torch.Tensor) -> torch.Tensor:
+    """float64 -> binary16 with ONE rounding (NumPy converts directly; torch's conversion passes through float32)"""
+    return torch.from_numpy(t64.contiguous().numpy().astype("float16"))
+
+
+def exact_input64(spec: Spec, ops: dict, skip=()) -> torch.Tensor:
+    """what the convolution reads, (n, c, h, w) float64 on the CPU: x [; t], times the SE gains, rounded to binary16, plus pre_add,
+    rounded to binary16.  skip: roundings left out (a WRONG order, for the share of elements that can tell)."""
+    x = ops["x"].cpu().double()
+    if spec.form == "cat":
+        x = torch.cat([ops["t"].cpu().double(), x], dim=1)
+    if spec.scaled:
+        x = x * ops["scale"].cpu().double()[:, :, None, None]        # 11 x 11 bits: exact in float64 (and in float32)
+        if "scale" not in skip:
+            x = _to_half_once(x).double()
+    if spec.pre_add:
+        x = x + ops["pre"].cpu().double()
+        if "pre" not in skip:
+            x = _to_half_once(x).double()
+    return x
+
+
+def exact_epilogue(spec: Spec, acc64, e1=None, e2=None, skip=()) -> dict:
+    """acc64 = conv + bias, exact in float64 -> {"y": fp16, "y2": fp16} per extra_mode, any layout.  The accumulator (with e1 in
+    modes 1 and 4) must be a float32 number -- the validity condition; from there the arithmetic is the epilogue's, in float32:
+    the activation max(t, t * slope) with the PRODUCT rounded to float32, the adds of modes 2 .. 5 as float32 sums (exact under
+    every recipe except mode 2's act + e1 behind a negative t, where the float32 sum is rounded before the store rounds it)."""
+    m = spec.mode
+    t64 = acc64 + e1.double() if m in (1, 4) else acc64
+    t = t64.float()
+    assert bool((t.double() == t64).all()), "the case is not exact: an accumulator is no float32 number"
+    u = t * torch.tensor(LEAK if spec.act else 1.0, dtype=torch.float32)
+    a = torch.maximum(t, u)
+    if m == 2:
+        return {"y": (a + e1.float()).half()}
+    inner = a if "act" in skip else a.half().float()
+    if m == 3:
+        return {"y": (inner + e1.float() + e2.float()).half()}
+    if m in (4, 5):
+        return {"y": a.half(), "y2": (inner + e2.float()).half()}
+    return {"y": a.half()}
+
+
+def exact_acc64(spec: Spec, xin64: torch.Tensor, ops: dict) -> torch.Tensor:
+    """conv + bias of the whole batch in float64 on the CPU"""
+    if spec.up:
+        xin64 = F.interpolate(xin64, scale_factor=2, mode="nearest")
+    return F.conv2d(xin64.contiguous(), ops["w"].cpu().double().contiguous(), ops["b"].cpu().double(), 1, spec.pad, spec.dil)
+
+
+def expected_exact(spec: Spec, ops: dict, skip=()) -> dict:
+    """every output of the form ("y", "y2", "pool" (n, k, H, W) views; "mean" (n, k)) as the binary16 tensor the contract of the
+    module docstring defines, computed in float64 on the CPU from the fp16 operands:
+      the SE product x * s, then + pre_add, each rounded to binary16;  the activation max(t, t * slope), product in float32;
+      mode 3: fp16(act) + e1 + e2;  modes 4 and 5: y2 = fp16(y) + e2;  pool: the max-pool of the produced binary16 tensor;
+      mean: fp16(sum fp16(y) * fl32(1 / hw)), sum and product exact, one rounding."""
+    acc = exact_acc64(spec, exact_input64(spec, ops, skip), ops)
+    e1 = ops["e1"].cpu() if "e1" in ops else None
+    e2 = ops["e2"].cpu() if "e2" in ops else None
+    out = exact_epilogue(spec, acc, e1, e2, skip)
+    if spec.pooled:
+        out["pool"] = max_pool_binary16(out["y2" if spec.has_y2 else "y"])
+    if spec.has_mean:
+        out["mean"] = mean_binary16(out["y"])
+    return out
+
+
+def max_pool_binary16(t: torch.Tensor) -> torch.Tensor:
+    """2x2 max-pool of an fp16 tensor with the maximum of IEEE 754-2019, which orders -0 below +0 (the packed binary16 maximum of
+    the kernels does; torch's max_pool2d keeps whichever zero it met first).  Both zeros occur under the `subnormal` recipe."""
+    m = F.max_pool2d(t.float(), 2, 2)
+    plus = F.max_pool2d((t.contiguous().view(torch.int16) == 0).float(), 2, 2) > 0          # a +0 in the window
+    zero = torch.zeros_like(m)
+    return torch.where(m == 0, torch.where(plus, zero, -zero), m).half()
+
+
+def mean_binary16(y: torch.Tensor) -> torch.Tensor:
+    """(n, k, H, W) fp16 -> (n, k) fp16 channel means as the kernels form them (csrc/posepaf_epilogue.hip: k_channel_mean_finish,
+    k_se_gains): the exact sum TIMES the float32 reciprocal of the pixel count, the exact product rounded to binary16 once"""
+    inv = (torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(y.shape[2] * y.shape[3]), dtype=torch.float32)).double()
+    return _to_half_once(y.double().sum(dim=(2, 3)) * inv)
+
+
+def _on_grid(t, grid: float) -> bool:
+    q = t.double() / grid
+    return bool((q == q.round()).all())
+
+
+def assert_exact_case(spec: Spec, ops: dict, recipe: str, want: dict, label: str) -> dict:
+    """The conditions under which bit equality may be asked of ANY summation order, asserted on the reference before anything is
+    compared (a case that breaks one is a bug of the test, not a finding):
+      per output element  sum |x * w| + |b| + |e1| + |e2| < 2^24  in units of the operands' grid (0.5; 2^-24 under `subnormal`), and
+      every conv input and added tensor on that grid: every fp32 partial sum is exact in every order;
+      every expected output finite;
+      channel sums: every y on a grid (1; 2^-24) with sum |y| < 2^24 grid units per image and channel;
+      subnormal: every input value and every expected output is a binary16 subnormal or zero;
+      rounding: per inner rounding of the form, the share of elements of the output behind it that differ between the contract's order
+      and the order WITHOUT that rounding is > 0, and the share of elements any of them changes is >= 1 %.
+    -> {"abs_sum_max": grid units, "shares": {rounding: share, "any": share}}"""
+    grid = SUBNORMAL_UNIT if recipe == "subnormal" else 0.5
+    xin = exact_input64(spec, ops)
+    added = [ops[n_].cpu().double() for n_ in ("e1", "e2") if n_ in ops]
+    for t in [xin, ops["b"].cpu()] + added:
+        assert _on_grid(t, grid), f"{label} [{recipe}]: an operand is off the grid {grid}"
+    s_abs = dict(ops, w=ops["w"].abs(), b=ops["b"].abs())
+    a = exact_acc64(spec, xin.abs(), s_abs)
+    for t in added:
+        a = a + t.abs()
+    abs_max = float(a.max()) / grid
+    assert abs_max < EXACT_LIMIT, f"{label} [{recipe}]: sum |x w| + |b| + |e| reaches {abs_max:.4g} grid units: fp32 sums are not exact"
+    for name, v in want.items():
+        assert bool(torch.isfinite(v.float()).all()), f"{label} [{recipe}]: expected {name} is not finite"
+    if spec.has_mean:
+        ygrid = SUBNORMAL_UNIT if recipe == "subnormal" else 1.0
+        y = want["y"].double()
+        assert _on_grid(y, ygrid), f"{label} [{recipe}]: outputs off the grid {ygrid}: their fp32 sum depends on the order"
+        tot = float(y.abs().sum(dim=(2, 3)).max()) / ygrid
+        assert tot < EXACT_LIMIT, f"{label} [{recipe}]: sum |y| reaches {tot:.4g} grid units"
+    if recipe == "subnormal":
+        lim = 2.0 ** -14
+        for name in [n_ for n_ in ("x", "t", "b", "e1", "e2", "pre") if n_ in ops]:
+            assert float(ops[name].abs().max()) < lim, f"{label}: operand {name} is not subnormal"
+        assert float(xin.abs().max()) < lim
+        for name, v in want.items():
+            assert float(v.float().abs().max()) < lim, f"{label}: expected {name} leaves the subnormal range"
+    shares = {}
+    if recipe == "rounding":
+        anyd = None
+        for r in inner_roundings(spec):
+            other = expected_exact(spec, ops, skip=(r,))
+            name = "y2" if (r == "act" and spec.has_y2) else "y"
+            d = want[name].view(torch.int16) != other[name].view(torch.int16)
+            shares[r] = float(d.float().mean())
+            anyd = d if anyd is None else (anyd | d)
+            assert shares[r] > 0, f"{label}: no element can tell whether the rounding `{r}` happens"
+        shares["any"] = float(anyd.float().mean())
+        assert shares["any"] >= 0.01, f"{label}: only {shares['any']:.3%} of the elements depend on the rounding order"
+    return {"abs_sum_max": abs_max, "shares": shares}
+
+
+def first_bit_difference(got: torch.Tensor, want: torch.Tensor, label: str):
+    """None when two fp16 tensors ((n, k, H, W), or (n, k) channel means) hold the same BITS, else a message naming the first
+    differing image, its tile and pixel, the channel and both values"""
+    if got.dim() == 2:
+        got, want = got[:, :, None, None], want[:, :, None, None]
+    g, w = got.contiguous().view(torch.int16), want.to(got.device).contiguous().view(torch.int16)
+    bad = g != w
+    if not bool(bad.any()):
+        return None
+    n_bad = int(bad.sum())
+    zeros = int((bad & ((g & 0x7FFF) == 0) & ((w & 0x7FFF) != 0)).sum())     # a flush shows as zeros where a value is due
+    i, ch, y, x = (int(v) for v in bad.permute(0, 2, 3, 1).nonzero()[0][[0, 3, 1, 2]])
+    H, W = got.shape[2:]
+    return (f"{label}: {n_bad} of {bad.numel()} elements differ ({zeros} of them are zero where a value is expected, largest "
+            f"|difference| {float((got.double() - want.to(got.device).double()).abs().nan_to_num(float('inf')).max()):.6g}); "
+            f"first: image {i}, tile {tile_of(H, W, y, x)} at pixel (y {y}, x {x}), "
+            f"channel {ch}: got {float(got[i, ch, y, x])!r} (0x{int(g[i, ch, y, x]) & 0xFFFF:04x}), "
+            f"expected {float(want[i, ch, y, x])!r} (0x{int(w[i, ch, y, x]) & 0xFFFF:04x})")

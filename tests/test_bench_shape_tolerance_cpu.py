@@ -2,7 +2,9 @@
 bench geometry (profiles/conv_choice_b128.json).  Per key, on the same operand recipe at 2 samples: a "kernel" that drops ONE input
 channel at ONE tap over ONE tile of the last image must be rejected, and the float64 truth rounded to fp16 must be accepted.
 The tolerance scale max |ref| comes from an fp32 torch.nn.functional pass over the whole 2-sample output; float64 is computed
-for the mutated tile only."""
+for the mutated tile only.
+The keys on the `strengthened` printout are where this bar cannot see ONE missing term: tests/test_gpu_conv_exact.py (exact
+operands, bit equality; tests/test_conv_exact_reference_cpu.py shows one missing term changes a bit at every key) closes that gap."""
 import pytest
 import torch
 
