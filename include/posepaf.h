@@ -51,9 +51,14 @@ typedef enum {
 typedef enum { PP_F32 = 0, PP_F16 = 1 } pp_dtype;
 
 /* per-image status bits in pp_record.status */
-#define PP_ST_PEAK_OVERFLOW 1u   /* a keypoint channel had more peaks than max_peaks_per_part (extra dropped) */
-#define PP_ST_HUMAN_OVERFLOW 2u  /* more than PP_MAX_HUMANS people after pruning (extra dropped) */
-#define PP_ST_SKEL_OVERFLOW 4u   /* more live partial skeletons than the assembly table holds */
+#define PP_ST_PEAK_OVERFLOW 1u   /* a keypoint channel had more peaks than max_peaks_per_part: per part the first
+                                    max_peaks_per_part peaks in row-major order of the map are kept, and peak ids are numbered
+                                    over the KEPT peaks (parts in order, no gaps) -- the record is what the reference gives on
+                                    that truncated joint list; n_peaks counts the kept peaks; pp_read_peaks refuses */
+#define PP_ST_HUMAN_OVERFLOW 2u  /* more than PP_MAX_HUMANS people after pruning: the first PP_MAX_HUMANS in the reference's
+                                    order are kept.  Never raised by the Python rules, whose table (next bit) is as large */
+#define PP_ST_SKEL_OVERFLOW 4u   /* more live partial skeletons than the assembly table holds: 256 with the C++ rules,
+                                    128 with the Python rules (pp_process_batch_py and the original path) */
 #define PP_ST_SORT_UNDEFINED 8u  /* the reference's std::sort (non-strict comparator, pafprocess.cpp:333-335)
                                     would have read outside its array on this input: its result is undefined */
 #define PP_ST_CAND_OVERFLOW 16u  /* more accepted limb candidates for one limb than the kernel holds */
