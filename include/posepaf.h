@@ -743,7 +743,11 @@ PP_API int pp_get_test_cfg(const pp_ctx *ctx, pp_test_cfg *cfg);
  * Two plain launches on `stream`: per-workgroup partials into the workspace (never assumed zero, never needs clearing), then a
  * reduction in a fixed order that multiplies by inv_loss_scale once.  No floating-point atomics: the order of the float32 additions
  * follows from (m, c_in, c_out) alone, so the result is bit-equal from run to run, eager or replayed from a graph, at every pointer
- * alignment the entry accepts.  Asynchronous, allocates nothing, needs no pp_ctx, capturable.
+ * alignment the entry accepts (g on any 2-byte boundary with any ldg >= c_out, x and scale on any 16-byte one).  Non-finite inputs
+ * stay non-finite and stay where they belong: an infinite or NaN g[m][k] makes row k of dw and db[k] non-finite, a non-finite
+ * xs[m][c] (an infinite or NaN x, or a product with the gain above 65504) makes column c of dw non-finite in all c_out rows, every
+ * other element keeps the bits it has without that input; whether an affected element is an infinity or a NaN is unspecified.
+ * Asynchronous, allocates nothing, needs no pp_ctx, capturable.
  * Refusals (nothing launched, outputs untouched), in this order:  PP_ERR_BAD_ARG: a null g, x, dw, db or workspace; m <= 0, hw <= 0,
  * m % hw != 0 with a scale; ldg < c_out; x or scale off a 16-byte boundary, g off a 2-byte one, dw, db or the workspace off a 4-byte
  * one; inv_loss_scale not finite and positive.  PP_ERR_UNSUPPORTED: pp_head_wgrad_supported is 0, or a scale with hw % 64 != 0 (the
