@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "../../include/posepaf.h"
+#include "posepaf_halo_schedule.h"
 
 namespace {
 
@@ -514,9 +515,8 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
     constexpr int PT = PM / 16;          // 8
     constexpr int CT = 4;
     constexpr int WB = BN * 32 * 2;      // weight slice of one phase: 8 sub-tiles, one per wave
-    constexpr int KEEP = 3;              // phases whose DMA may still be in flight when a phase ends (this one and 2 before)
     constexpr int NW = 6;                // weight ring
-    constexpr int AHEAD = NW - 1;        // the slice of phase ph + AHEAD is issued while phase ph is multiplied, into the slot phase ph - 1 read
+    constexpr int AHEAD = 5;             // the slice of phase ph + AHEAD is issued while phase ph is multiplied, into the slot phase ph - 1 read
     constexpr int HP = 56;               // halo pieces per buffer: 7 per wave (pieces past the halo are zero-page reads)
 #ifdef PP_HALO_NPW7   // A/B build (tools): seven pieces on every tile width
     constexpr int NPW = 7;
@@ -524,6 +524,8 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
     constexpr int NPW = (LGTW == 7 || D > 1) ? 7 : 6;   // pieces a wave really loads: the narrower tiles' halos (<= 45 pieces) need six
 #endif
     static_assert(BN == 128, "one weight sub-tile per wave and phase");
+    using S = halo_schedule::Schedule<NT, NPW, AHEAD, NW>;   // what the main loop issues when, and every wait count that follows from it
+    using LR = halo_schedule::Reads<PT>;
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int halo_bytes = HP * SUB;
     unsigned char *s_halo = smem;                               // [2][56 KiB]
@@ -675,12 +677,12 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
         lds_read16<Chi>(dst, R[k][f]);
     };
 
-    // first DMA of a tile: halo of channel block 0 (7 pieces per wave) into buffer 0 and the weight slices of phases 0..AHEAD-1
+    // first DMA of a tile: halo of channel block 0 (the schedule's pieces, all at once) into buffer 0 and the weight slices of phases 0..AHEAD-1
     auto stage_first = [&]() {
         st_cb = 0, st_tap = 0, st_slot = 0;
 #pragma unroll
-        for (int t = 0; t < NPW; t++)
-            if (t < 4 || (t == 4 && p4) || (t == 5 && p5) || (t == 6 && p6)) stage_halo(t, 0, 0);
+        for (int t = 0; t < S::NPW; t++)
+            if (t < S::OPTIONAL || (t == 4 && p4) || (t == 5 && p5) || (t == 6 && p6)) stage_halo(t, 0, 0);
         for (int q = 0; q < AHEAD && q < np; q++) stage_w();
     };
     unsigned long long acc_t[6] = {0, 0, 0, 0, 0, 0}, t_prev = 0;   // DIAGNOSTIC (MASK bit 1024): cycles per section, summed over tiles
@@ -739,13 +741,9 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
     //           became free when the previous phase ended);
     //   half B: 8 pixel tiles x channel tiles 2, 3;  at its start weight fragments 0, 1 of the NEXT phase are read, and after
     //           the two MFMAs of pixel tile i its fragment of the next phase (next tap: the same halo, shifted).
-    // LDS returns data in order, so lgkmcnt is counted like vmcnt: before pixel tile i of half A the reads issued after ITS
-    // fragment are tiles i+1..7 of the previous phase and this phase's two weight reads: lgkmcnt(9 - i).
-    // DMA schedule of a wave, per tap: one weight sub-tile (slice ph + AHEAD, into the ring slot phase ph - 1 read from), plus,
-    // while a next channel block exists, its halo pieces: 2, 2, 1, 1 (, 1) at taps 0..3 (4) -- every piece is KEEP phases old when tap
-    // 7 ends.  After the MFMAs the wave waits until only the DMA of the last KEEP phases is in flight (counted vmcnt; the
-    // count is the schedule's, a compile-time sum), then the barrier publishes what landed: the weight slice of phase ph + 2,
-    // whose fragments 0, 1 are read in half B of the next phase.  No dummy DMA anywhere.
+    // Which DMA a tap issues, the counted s_waitcnt vmcnt that ends it (never 0 inside the loop, no dummy DMA anywhere) and the
+    // counted lgkmcnt before each use of a fragment all come from ONE schedule: posepaf_halo_schedule.h (S, LR).  After its MFMAs a
+    // wave waits until only the loads S::in_flight allows are outstanding, then the barrier publishes what landed.
     int ph = 0;
     const int grp = wave >> 2;   // waves w and w + 4 share a SIMD
     unsigned long long rt0 = 0;
@@ -755,38 +753,26 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
         constexpr int tap = decltype(TAP)::value;
         constexpr bool halo = decltype(HALO)::value;     // a next channel block exists: its halo streams in
         constexpr int ntap = tap == NT - 1 ? 0 : tap + 1;
-        // halo pieces issued per tap.  A piece is waited for KEEP = 3 taps after its issue and must have landed when the block ends:
-        // nine taps spread them 2-2-1-1(-1) over taps 0..3 (4), four taps issue all NPW at tap 0.
-        constexpr auto halo_at = [](int t) { return t < 0 ? 0 : (NT == 9 ? (t <= 1 ? 2 : (t <= NPW - 3 ? 1 : 0)) : (t == 0 ? NPW : 0)); };
-        // The NEW halo buffer is first read by the fragment refill in half B of the block's LAST tap (after flip_R), so its pieces
-        // must have landed when the tap before that ends.  Nine taps: the last piece is issued at tap 4 and is KEEP phases old
-        // when tap 7 ends.  Four taps: every piece is issued at tap 0 and must be down when tap 2 ends -- only the three weight
-        // slices issued after them may still be in flight there (counting the pieces of "the last three taps" at tap 2 let the
-        // refill read a halo that was still arriving: wrong pixels under load, found by tools/collapsed_repeat.py).
-        constexpr int in_flight = KEEP + (!halo ? 0 : NT == 9 ? halo_at(tap) + halo_at(tap - 1) + halo_at(tap - 2) : (tap <= 1 ? NPW : 0));
-        static_assert(KEEP == 3, "in_flight sums the halo pieces of three taps");
+        constexpr int in_flight = S::in_flight(tap, halo);
+        auto issue_piece = [&](auto K) {   // piece k of the next block's halo, where the schedule issues it at this tap and the wave owns it
+            constexpr int k = decltype(K)::value;   // (compile-time: hsrc[] and the LDS destination are indexed by it)
+            if constexpr (halo && k < S::NPW && S::issue_tap(k) == tap) {
+                if constexpr (k < S::OPTIONAL) stage_halo(k, cb + 1, (cb + 1) & 1);
+                else if (k == 4 ? p4 : (k == 5 ? p5 : p6)) stage_halo(k, cb + 1, (cb + 1) & 1);
+            }
+        };
         // The two waves of a SIMD (w and w + 4) issue their DMA at different times: a piece blocks its wave for 60-100 cycles, and
         // with both waves there at once right after the barrier the matrix pipe idles; group 1 issues between the halves.
         auto issue_dma = [&]() {
             if (!(dbg & 1)) {
-                if (halo) {
-                    if (NT == 4) {
-                        if (tap == 0) {
-                            stage_halo(0, cb + 1, (cb + 1) & 1);
-                            stage_halo(1, cb + 1, (cb + 1) & 1);
-                            stage_halo(2, cb + 1, (cb + 1) & 1);
-                            stage_halo(3, cb + 1, (cb + 1) & 1);
-                            if (p4) stage_halo(4, cb + 1, (cb + 1) & 1);
-                            if (p5) stage_halo(5, cb + 1, (cb + 1) & 1);
-                            if (NPW == 7 && p6) stage_halo(6, cb + 1, (cb + 1) & 1);
-                        }
-                    } else if (tap <= 1) {
-                        stage_halo(2 * tap, cb + 1, (cb + 1) & 1);
-                        stage_halo(2 * tap + 1, cb + 1, (cb + 1) & 1);
-                    } else if (tap <= NPW - 3) {
-                        if (tap == 2 ? p4 : (tap == 3 ? p5 : p6)) stage_halo(tap + 2, cb + 1, (cb + 1) & 1);
-                    }
-                }
+                static_assert(S::pieces_before_slice, "the schedule counts a tap's pieces before its weight slice");
+                issue_piece(std::integral_constant<int, 0>{});
+                issue_piece(std::integral_constant<int, 1>{});
+                issue_piece(std::integral_constant<int, 2>{});
+                issue_piece(std::integral_constant<int, 3>{});
+                issue_piece(std::integral_constant<int, 4>{});
+                issue_piece(std::integral_constant<int, 5>{});
+                issue_piece(std::integral_constant<int, 6>{});
                 if (ph + AHEAD < np) stage_w();
             }
         };
@@ -801,7 +787,8 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
         }
         auto tile_a = [&](auto I) {
             constexpr int i = decltype(I)::value;
-            wait_lgkmcnt<9 - i>();
+            static_assert(LR::before_tile_a(i) == 9 - i, "pixel tiles i + 1 .. 7 of the previous phase and this phase's two weight reads");
+            wait_lgkmcnt<LR::before_tile_a(i)>();
             if (!(dbg & 2)) {
                 mfma_acc(acc[i][0], wf[0], xf[i]);
                 mfma_acc(acc[i][1], wf[1], xf[i]);
@@ -823,7 +810,8 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
             lds_read16<0>(wf[0], sw_nxt);
             lds_read16<SUB>(wf[1], sw_nxt);
         }
-        wait_lgkmcnt<refill ? 2 : 0>();
+        static_assert(LR::before_half_b(true) == 2 && LR::before_half_b(false) == 0, "the next phase's wf[0], wf[1]");
+        wait_lgkmcnt<LR::before_half_b(refill)>();
         if (refill && tap == NT - 1) flip_R((cb + 1) & 1);   // the next phase is tap 0 of the next channel block: the other halo buffer
         auto tile_b = [&](auto I) {
             constexpr int i = decltype(I)::value;
@@ -845,13 +833,9 @@ __global__ __launch_bounds__(NTHREADS) void k_conv3x3_halo(const ConvParams p, c
         tile_b(std::integral_constant<int, 6>{});
         tile_b(std::integral_constant<int, 7>{});
         __builtin_amdgcn_s_setprio(0);
-        // pieces this wave did NOT issue inside the window of this tap's wait (piece 4 / 5 / 6 goes out at tap 2 / 3 / 4 of nine and
-        // stays in the window for three taps; all go out at tap 0 of four and stay for taps 0 and 1): wave-uniform, 0 .. 3
-        constexpr bool w4 = halo && (NT == 9 ? (tap >= 2 && tap <= 4) : tap <= 1);
-        constexpr bool w5 = halo && (NT == 9 ? (tap >= 3 && tap <= 5) : tap <= 1);
-        constexpr bool w6 = halo && NPW == 7 && (NT == 9 ? (tap >= 4 && tap <= 6) : tap <= 1);
+        // pieces this wave does not own inside the window of this tap's wait: wave-uniform, 0 .. 3
+        constexpr bool w4 = halo && S::in_window(4, tap), w5 = halo && S::in_window(5, tap), w6 = halo && S::in_window(6, tap);
         const int missing = (w4 && !p4) + (w5 && !p5) + (w6 && !p6);
-        static_assert(in_flight >= 3, "the window always holds the three weight slices");
         if (ph + AHEAD >= np) wait_vmcnt<0>();     // the last phases issue nothing: nothing to wait for
         else if (missing == 0) wait_vmcnt<in_flight>();
         else if (missing == 1) wait_vmcnt<(in_flight > 1 ? in_flight - 1 : 0)>();

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Instruction diff of kernels between two device-assembly listings of posepaf_kernels.hip (no GPU needed).
+"""Instruction diff of kernels between two device-assembly listings of one kernel source of the library (no GPU needed).
 
-The default test configuration must keep launching the instances with the literals, instruction for instruction.  Emit the
-listing of each revision with the library's own flags
+A change that must not move a kernel -- the default test configuration of posepaf_kernels.hip keeps launching the instances with
+the literals, the halo convolution of posepaf_conv_own.hip keeps its hand-placed main loop -- is shown instruction for instruction.
+Emit the listing of each revision of the source with the library's own flags
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -fvisibility=hidden -ffp-contract=off -fno-fast-math -DPP_BUILDING \
-          --cuda-device-only -S improved-body-parts_amd/csrc/posepaf_kernels.hip -o <rev>.s
+          --cuda-device-only -S improved-body-parts_amd/csrc/<source>.hip -o <rev>.s
 
-and run `default_asm_diff.py parent.s new.s [name-substring ...]`.  For every kernel present in both listings whose symbol
-contains one of the substrings (default: the Python-rule and full-resolution kernels) the instruction streams are compared
+and run `default_asm_diff.py parent.s new.s [name-substring ...]` (e.g. `k_conv3x3_halo`).  For every kernel present in both listings
+whose symbol contains one of the substrings (default: the Python-rule and full-resolution kernels of posepaf_kernels.hip; pass ''
+for every kernel of the listing) the instruction streams are compared
 after dropping comments, labels' numbering and assembler directives, and the resource lines (.vgpr_count, .sgpr_count, LDS, scratch)
 are printed.  Exit status 1 when any compared kernel differs."""
 import re
