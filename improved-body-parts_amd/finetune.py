@@ -5,7 +5,8 @@
         [--stages 4] [--train all|heads] [--lr 2.5e-5] [--loss device|torch] [-p weights.pth] [--seed 0] [--save out.pth]
         [--augment [--src_sizes HxW[,HxW...]]]
     python finetune.py --model fused --train heads --synthetic 64 --batch 8 --sizes 512x512 --steps 20 \\
-        [--arch posenet|final|auto] [-p weights.pth] [--stages 4] [--loss_scale auto|N] [--wgrad device|torch]
+        [--arch posenet|final|auto] [-p weights.pth] [--stages 4] [--loss_scale auto|N|dynamic] [--wgrad device|multi|torch]
+        [--update torch|device] [--graph] [--growth_interval 2000]
     python finetune.py --ann_file person_keypoints_train2017.json --img_dir train2017 [--limit N] --batch 8 --sizes 512x512 --steps 20 ...
 
 Per step: a batch of synthetic images (random uint8 pixels, divided by 255 on the device by pp_preprocess_u8) and their
@@ -46,10 +47,18 @@ evaluate.py -p loads); val_loss.focal_l2_terms -> combine -> backward() (pp_foca
                   tensors with a float64 matmul, for A/B; --arch as evaluate.py's.  The data path (--synthetic, --augment, --ann_file)
                   is the same; --save writes {'weights': HeadTrainer.state_dict()}, which evaluate.py -p loads.  The JSON line gains
                   "model": "fused", "wgrad", "loss_scale" and "skipped_steps" (steps whose gradient was not finite: no update)
+  --update device (with --model fused) pp_head_update_f32 in place of torch.optim.SGD.step(), the masked restore and the fp16 copies;
+                  --wgrad multi: every head's gradient in one pp_head_wgrad_multi_f16 call; --loss_scale dynamic (needs --update device
+                  and --wgrad multi or torch): apex's dynamic scaler on the device, doubling after --growth_interval finite steps;
+                  --graph (implies --update device): the first step eager, the second captured into one graph, the rest replayed, the
+                  losses read once after the last step.  The JSON line gains "graph", "update",
+                  "graph_replays" and "loss_scale_last"
 
 Prints one JSON line: losses (per step), loss_first, loss_last, grad_norm_first (L2 norm of the updated parameters' gradients at
-step 0), seconds, loss, train, images_per_step (and "augment": true with --augment; with --ann_file also "source": "annotations",
-instances, instances_skipped, images_skipped_multi_crowd).  Combinations it does not support end with a message before the GPU is touched.
+step 0), seconds, steps_per_s (steady state: from the second step on, with --graph from the third, so without the first step's set-up
+and the capture; null when no such step was made), loss, train, images_per_step (and "augment": true with --augment; with --ann_file
+also "source": "annotations", instances, instances_skipped, images_skipped_multi_crowd).  Combinations it does not support end with a
+message before the GPU is touched.
 """
 import argparse
 import ctypes as C
@@ -88,11 +97,20 @@ def parse(argv=None):
     ap.add_argument("--limit", type=int, default=0, help="with --ann_file: only the first N images that have a person annotation")
     ap.add_argument("--model", choices=("plain", "fused"), default="plain", help="fused: train the heads on the fused fp16 forward")
     ap.add_argument("--arch", choices=("posenet", "final", "auto"), default="posenet", help="with --model fused: the architecture")
-    ap.add_argument("--loss_scale", default="auto", help="with --model fused: 'auto' or a power of two")
-    ap.add_argument("--wgrad", choices=("device", "torch"), default="device", help="with --model fused: pp_head_wgrad_f16 or the torch A/B form")
+    ap.add_argument("--loss_scale", default="auto", help="with --model fused: 'auto', a power of two or 'dynamic'")
+    ap.add_argument("--wgrad", choices=("device", "torch", "multi"), default="device",
+                    help="with --model fused: pp_head_wgrad_f16 per head, the torch A/B form, or pp_head_wgrad_multi_f16 once")
+    ap.add_argument("--update", choices=("torch", "device"), default=None, help="with --model fused: torch.optim.SGD (default) or pp_head_update_f32")
+    ap.add_argument("--graph", action="store_true", help="with --model fused: capture the step in a graph (implies --update device)")
+    ap.add_argument("--growth_interval", type=int, default=None, help="with --loss_scale dynamic: finite steps before the scale doubles (2000)")
     a = ap.parse_args(argv)
     if a.ann_file:
         a.augment = True
+    a.update_given, a.growth_given = a.update is not None, a.growth_interval is not None
+    if a.update is None:
+        a.update = "device" if a.graph else "torch"
+    if a.growth_interval is None:
+        a.growth_interval = 2000
     return a
 
 
@@ -137,10 +155,19 @@ def refusals(a):
             out.append("--model fused trains the heads only (the fused model has no backward): pass --train heads")
         if a.loss != "device":
             out.append("--model fused takes the loss gradient from pp_focal_l2_grad: --loss torch belongs to --model plain")
-        if a.loss_scale != "auto" and not is_power_of_two(a.loss_scale):
-            out.append(f"--loss_scale {a.loss_scale}: 'auto' or a power of two (2^-24 .. 2^24)")
-    elif a.arch != "posenet" or a.loss_scale != "auto" or a.wgrad != "device":
-        out.append("--arch, --loss_scale and --wgrad belong to --model fused")
+        if a.loss_scale not in ("auto", "dynamic") and not is_power_of_two(a.loss_scale):
+            out.append(f"--loss_scale {a.loss_scale}: 'auto', 'dynamic' or a power of two (2^-24 .. 2^24)")
+        if a.graph and a.update != "device":
+            out.append("--graph captures the device update: it does not go with --update torch")
+        if a.loss_scale == "dynamic" and (a.update != "device" or a.wgrad == "device"):
+            out.append("--loss_scale dynamic needs --update device (or --graph) and --wgrad multi or torch: pp_head_wgrad_f16 takes its "
+                       "factor from the host")
+        if a.growth_interval < 0:
+            out.append("--growth_interval must be at least 0")
+        elif a.growth_given and a.loss_scale != "dynamic":
+            out.append("--growth_interval belongs to --loss_scale dynamic")
+    elif a.arch != "posenet" or a.loss_scale != "auto" or a.wgrad != "device" or a.graph or a.update_given or a.growth_given:
+        out.append("--arch, --loss_scale, --wgrad, --update, --graph and --growth_interval belong to --model fused")
     sizes = a.sizes.split(",")
     try:
         h, w = (int(v) for v in sizes[0].lower().split("x"))
@@ -333,7 +360,8 @@ def main(argv=None):
         from posepaf import head_train
         try:
             tr = head_train.HeadTrainer(net, dev, lr=a.lr, momentum=MOMENTUM, weight_decay=WEIGHT_DECAY, wgrad=a.wgrad,
-                                        loss_scale="auto" if a.loss_scale == "auto" else float(a.loss_scale))
+                                        loss_scale=a.loss_scale if a.loss_scale in ("auto", "dynamic") else float(a.loss_scale),
+                                        update=a.update, graph=a.graph, growth_interval=a.growth_interval)
         except _lib.PosePafError as e:
             raise SystemExit(f"finetune.py: --model fused: {e}")
         a.stages = tr.T
@@ -373,9 +401,13 @@ def main(argv=None):
     # images in one batch would make the batches, and their losses, as different as 1 + 2 people are from 3 + 4; ceil(N / B) steps see all
     per_pass = -(-N // B)
     losses, grad_norm_first = [], None
+    unsteady, t_steady = (2 if a.graph else 1), None      # steps in front of the steady state: the eager first one, and the capture
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for step in range(a.steps):
+        if step == unsteady:
+            torch.cuda.synchronize(dev)
+            t_steady = time.perf_counter()
         idx = (step + torch.arange(B, device=dev) * per_pass) % N
         mask = None
         if a.augment:
@@ -411,7 +443,8 @@ def main(argv=None):
         opt.step()
         losses.append(loss.detach())
     torch.cuda.synchronize(dev)
-    dt = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    dt = t1 - t0
     losses = [float(v) for v in losses]
     if fused:
         fused_model.save_table()
@@ -420,7 +453,10 @@ def main(argv=None):
     result = {"losses": losses, "loss_first": losses[0], "loss_last": losses[-1], "grad_norm_first": float(grad_norm_first),
               "seconds": dt, "loss": a.loss, "train": a.train, "images_per_step": B, "steps": a.steps, "stages": a.stages, "lr": a.lr}
     if fused:
-        result.update({"model": "fused", "wgrad": a.wgrad, "loss_scale": tr.loss_scale_for(B), "skipped_steps": int(tr.skipped_steps)})
+        result.update({"model": "fused", "wgrad": a.wgrad, "loss_scale": "dynamic" if tr.dynamic else tr.loss_scale_for(B),
+                       "skipped_steps": int(tr.skipped_steps), "graph": bool(a.graph), "update": a.update, "graph_replays": tr.graph_replays,
+                       "loss_scale_last": float(tr.loss_scale_now())})
+    result["steps_per_s"] = (a.steps - unsteady) / (t1 - t_steady) if t_steady is not None else None
     if a.augment:
         result["augment"] = True
     result.update(stats)

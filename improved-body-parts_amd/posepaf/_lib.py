@@ -47,7 +47,8 @@ EXPORTS = [
     "pp_coco_rows_f32", "pp_oks_match", "pp_render_scenes", "pp_focal_l2_workspace_bytes", "pp_focal_l2_terms",
     "pp_focal_l2_grad", "pp_augment_batch", "pp_coco_masks_workspace_bytes", "pp_coco_masks_u8",
     "pp_head_wgrad_supported", "pp_head_wgrad_chunk_pixels", "pp_head_wgrad_max_workgroups", "pp_head_wgrad_workspace_bytes",
-    "pp_head_wgrad_f16",
+    "pp_head_wgrad_f16", "pp_head_wgrad_multi_max_heads", "pp_head_wgrad_multi_workspace_bytes", "pp_head_wgrad_multi_f16",
+    "pp_head_update_workspace_bytes", "pp_head_update_f32",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -76,6 +77,23 @@ class TestCfg(C.Structure):
     """pp_test_cfg (include/posepaf.h)"""
     _fields_ = [("thre2", C.c_double), ("connect_ration", C.c_double), ("len_rate", C.c_double),
                 ("connection_tole", C.c_double), ("mid_num", C.c_int), ("offset_radius", C.c_int), ("remove_recon", C.c_int)]
+
+
+class HeadWgradDesc(C.Structure):
+    """pp_head_wgrad_desc (include/posepaf.h): the per-head arguments of pp_head_wgrad_f16"""
+    _fields_ = [("g", C.c_void_p), ("ldg", C.c_int), ("x", C.c_void_p), ("scale", C.c_void_p), ("m", C.c_long), ("hw", C.c_int),
+                ("c_in", C.c_int), ("c_out", C.c_int), ("dw", C.c_void_p), ("db", C.c_void_p)]
+
+
+class HeadUpdateDesc(C.Structure):
+    """pp_head_update_desc (include/posepaf.h)"""
+    _fields_ = [("w_off", C.c_longlong), ("w_len", C.c_longlong), ("b_off", C.c_longlong), ("b_len", C.c_longlong),
+                ("weight", C.c_void_p), ("bias", C.c_void_p), ("wpad", C.c_void_p), ("bpad", C.c_void_p)]
+
+
+# pp_head_update_state (include/posepaf.h)
+HEAD_UPDATE_STATE_DTYPE = np.dtype([("scale", "<f4"), ("inv_scale", "<f4"), ("good_steps", "<i4"), ("growth_interval", "<i4"),
+                                    ("min_scale", "<f4"), ("max_scale", "<f4"), ("skipped", "<i8")])
 
 
 def load():
@@ -146,6 +164,13 @@ def load():
     L.pp_head_wgrad_workspace_bytes.argtypes = [C.c_long, C.c_int, C.c_int]
     L.pp_head_wgrad_workspace_bytes.restype = C.c_longlong
     L.pp_head_wgrad_f16.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_longlong, vp, vp, vp]
+    L.pp_head_wgrad_multi_max_heads.argtypes = []
+    L.pp_head_wgrad_multi_workspace_bytes.argtypes = [C.c_int, C.POINTER(HeadWgradDesc)]
+    L.pp_head_wgrad_multi_workspace_bytes.restype = C.c_longlong
+    L.pp_head_wgrad_multi_f16.argtypes = [C.c_int, C.POINTER(HeadWgradDesc), C.c_float, vp, vp, C.c_longlong, vp]
+    L.pp_head_update_workspace_bytes.argtypes = [C.c_long]
+    L.pp_head_update_workspace_bytes.restype = C.c_longlong
+    L.pp_head_update_f32.argtypes = [vp, vp, vp, C.c_long, vp, C.c_int, vp, vp, vp, vp]
     L.pp_flip_average.argtypes =[vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_pwconv_supported.argtypes = [C.c_int, C.c_int]
     L.pp_pwconv_f16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int, vp]

@@ -5,7 +5,8 @@ with respect to the predictions (val_loss.focal_l2_grad) and, per head, the weig
 (pp_head_wgrad_f16).  The data gradient of no layer is needed: the plain `finetune.py --train heads` detaches the chain between the
 stages in the same way.
 
-    tr = HeadTrainer(net, device, lr=2.5e-5, momentum=0.9, weight_decay=1e-4, loss_scale="auto", wgrad="device", arch=None)
+    tr = HeadTrainer(net, device, lr=2.5e-5, momentum=0.9, weight_decay=1e-4, loss_scale="auto", wgrad="device", arch=None,
+                     update="torch", graph=False, growth_interval=2000, init_scale=None)
     loss = tr.step(x, target, mask=None)         # 0-d float64 device tensor, the UNSCALED combine(terms); asynchronous
     grads = tr.gradients(x, target, mask=None)   # {(t, s): (dw float32 (50, 256), db float32 (50,))}; no update
     sd = tr.state_dict()                         # the plain network's keys, outs.* replaced by the float32 masters
@@ -25,10 +26,23 @@ S and pp_head_wgrad_f16 multiplies the float32 sums by 1 / S once (exact).  "aut
 where tw_max = max(nw) / sum(nw) * max(sw) / sum(sw) / B is the largest term weight of this batch size, KEYPOINT_TASK_WEIGHT = 3.0
 the largest channel weight, M <= 1, and ELEMENT_BOUND = 12 bounds |2 d f + d^2 f'| for predictions in [-1, 2] and targets in [0, 1]
 (|d| <= 2, f <= 2, |f'| = 1: 2 * 2 * 2 + 4).  A prediction outside that range can still overflow: then dw / db are not finite, the
-step's update is masked out on the device and `skipped_steps` counts it.  The scale is static (no dynamic scaling).
+step's update is masked out on the device and `skipped_steps` counts it.  "auto" and a given power of two are static scales.
+
+The captured step.  wgrad="multi" forms every head's dw / db in one pp_head_wgrad_multi_f16 call (the bits of
+"device").  update="device" replaces torch.optim.SGD.step(), the masked restore and the 80 fp16 copies by pp_head_update_f32: finite
+test, SGD (torch's roundings), fp16 copies and the loss-scale state in two launches; lr, momentum and weight decay live in a device
+block set_lr() writes.  loss_scale="dynamic" (needs update="device" and wgrad "multi" or "torch") is apex's dynamic scaler on that
+state: halve on a non-finite gradient (the step is skipped), double after growth_interval finite steps, between 2^-24 and 2^24,
+from init_scale or, without one, "auto" of the first batch; loss_scale_now() reads it.  graph=True (needs update="device"): the first
+step() of a signature -- (shape and dtype of x, shape and dtype of target, mask given or not) -- runs eagerly (the tuner times its
+candidates there), the second captures forward, loss, gradients and update into one torch.cuda.CUDAGraph over static copies of the
+inputs and replays it, later ones copy the inputs in and replay: the same bits as graph=False, step for step.  graph=True sets
+torch.backends.cudnn.deterministic (the few MIOpen layers must add in one order for that to hold).
 """
 import ctypes as C
 import math
+
+import numpy as np
 
 from . import val_loss
 from ._lib import PosePafError
@@ -74,7 +88,8 @@ def _pixel_major(grad):
 
 
 class HeadTrainer:
-    def __init__(self, net, device, lr=2.5e-5, momentum=0.9, weight_decay=1e-4, loss_scale="auto", wgrad="device", arch=None):
+    def __init__(self, net, device, lr=2.5e-5, momentum=0.9, weight_decay=1e-4, loss_scale="auto", wgrad="device", arch=None,
+                 update="torch", graph=False, growth_interval=2000, init_scale=None):
         import torch
         from . import fused_model
         pn = getattr(net, "posenet", None)
@@ -89,10 +104,22 @@ class HeadTrainer:
         for name, v, ok in (("lr", lr, lambda v: v > 0), ("momentum", momentum, lambda v: 0 <= v < 1), ("weight_decay", weight_decay, lambda v: v >= 0)):
             if not (isinstance(v, (int, float)) and math.isfinite(v) and ok(v)):
                 raise PosePafError(f"{name} = {v!r} is out of range")
-        if loss_scale != "auto" and not is_power_of_two(loss_scale):
-            raise PosePafError(f"loss_scale = {loss_scale!r}: 'auto' or a power of two in 2^-24 .. 2^24")
-        if wgrad not in ("device", "torch"):
-            raise PosePafError(f"wgrad = {wgrad!r}: 'device' (pp_head_wgrad_f16) or 'torch' (the A/B formulation)")
+        dynamic = isinstance(loss_scale, str) and loss_scale == "dynamic"
+        if not dynamic and loss_scale != "auto" and not is_power_of_two(loss_scale):
+            raise PosePafError(f"loss_scale = {loss_scale!r}: 'auto', 'dynamic' or a power of two in 2^-24 .. 2^24")
+        if wgrad not in ("device", "torch", "multi"):
+            raise PosePafError(f"wgrad = {wgrad!r}: 'device' (pp_head_wgrad_f16), 'multi' (pp_head_wgrad_multi_f16) or 'torch' (the A/B formulation)")
+        if update not in ("torch", "device"):
+            raise PosePafError(f"update = {update!r}: 'torch' (torch.optim.SGD) or 'device' (pp_head_update_f32)")
+        if graph and update != "device":
+            raise PosePafError("graph=True needs update='device': torch.optim.SGD.step() is not captured")
+        if dynamic and (update != "device" or wgrad == "device"):
+            raise PosePafError("loss_scale='dynamic' needs update='device' and wgrad 'multi' or 'torch': pp_head_wgrad_f16 takes its "
+                               "factor from the host")
+        if isinstance(growth_interval, bool) or not isinstance(growth_interval, int) or not 0 <= growth_interval < 2 ** 31:
+            raise PosePafError(f"growth_interval = {growth_interval!r}: an integer >= 0 (0: the scale never moves)")
+        if init_scale is not None and not is_power_of_two(init_scale):
+            raise PosePafError(f"init_scale = {init_scale!r}: None or a power of two in 2^-24 .. 2^24")
         from models import posenet_final
         found = "final" if isinstance(pn, posenet_final.PoseNet) else "posenet"
         if arch not in (None, found):
@@ -103,6 +130,9 @@ class HeadTrainer:
                     raise PosePafError(f"outs[{t}][{s}] is not a bare 1 x 1 convolution with a bias: a head with BN or an activation is refused")
         self.net, self.device, self.arch, self.wgrad = net, device, found, wgrad
         self.loss_scale_arg = loss_scale
+        self.update, self.graph, self.dynamic, self.graph_replays = update, bool(graph), dynamic, 0
+        if graph:
+            torch.backends.cudnn.deterministic = True
         self.model = fused_model.FusedIMHN.from_network(net, folded_merge=False).eval().to(device).half().to(memory_format=torch.channels_last)
         self.T, self.K = self.model.S, self.model.K
         self.heads = {(t, s): self.model.head[t][s] for t in range(self.T) for s in range(self.K)}
@@ -135,6 +165,11 @@ class HeadTrainer:
                 self.opt.state[p]["momentum_buffer"] = buf
         self.skipped_steps = torch.zeros((), dtype=torch.int64, device=device)
         self.last_inputs, self._seen, self._workspace = {}, {}, None
+        self._tw, self._graphs, self._last_batch = {}, {}, None
+        self._nw = torch.tensor([float(v) for v in self.nstack_weight[:self.T]], dtype=torch.float64, device=device)
+        self._sw = torch.tensor([float(v) for v in val_loss.SCALE_WEIGHT[:self.K]], dtype=torch.float64, device=device)
+        if update == "device":
+            self._init_device_update(sizes, lr, momentum, weight_decay, growth_interval if dynamic else 0, init_scale if dynamic else None)
         for key, head in self.heads.items():
             head.register_forward_pre_hook(lambda mod, args, key=key: self._seen.__setitem__(key, args[0]))
         self._push_masters()
@@ -142,7 +177,101 @@ class HeadTrainer:
     # ---- pieces of a step
 
     def loss_scale_for(self, batch):
+        """the static scale of a batch size ("auto" or the given power of two); the dynamic one lives on the device: loss_scale_now()"""
+        if self.dynamic:
+            raise PosePafError("loss_scale='dynamic' has no per-batch value: read loss_scale_now()")
         return auto_loss_scale(batch, self.T, self.K, self.nstack_weight) if self.loss_scale_arg == "auto" else float(self.loss_scale_arg)
+
+    def loss_scale_now(self):
+        """the loss scale the next step multiplies by -> 0-d float32 device tensor (a copy).  Dynamic: the device state; static: the
+        scale of the last batch size (before any step: PosePafError)"""
+        import torch
+        if self.dynamic:
+            if not self._scale_set:
+                raise PosePafError("without init_scale the dynamic scale starts at 'auto' of the first batch: no step was made yet")
+            return self._scale.clone()
+        if self._last_batch is None:
+            raise PosePafError("no step was made yet: loss_scale_for(batch) gives the static scale of a batch size")
+        return torch.tensor(self.loss_scale_for(self._last_batch), dtype=torch.float32, device=self.device)
+
+    def set_lr(self, lr):
+        """a new learning rate from the next step on: the optimiser's group, or with update='device' the device block (a captured step
+        reads it when it runs)"""
+        if not (isinstance(lr, (int, float)) and math.isfinite(lr) and lr > 0):
+            raise PosePafError(f"lr = {lr!r} is out of range")
+        if self.update == "device":
+            self._hyper[0] = float(lr)
+        else:
+            for group in self.opt.param_groups:
+                group["lr"] = float(lr)
+
+    # ---- update='device': pp_head_update_f32 and its blocks
+
+    def _init_device_update(self, sizes, lr, momentum, weight_decay, growth_interval, init_scale):
+        import torch
+        from . import _lib
+        L = _lib.load()
+        if len(self.heads) > L.pp_head_wgrad_multi_max_heads():
+            raise PosePafError(f"{len(self.heads)} heads: pp_head_update_f32 takes {L.pp_head_wgrad_multi_max_heads()}")
+        dev = self.device
+        self._hyper = torch.tensor([lr, momentum, weight_decay], dtype=torch.float32, device=dev)
+        self._state = torch.zeros(_lib.HEAD_UPDATE_STATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        f = self._state.view(torch.float32)
+        self._scale, self._inv_scale = f[0], f[1]                    # 0-d views of the block the kernel updates
+        self.skipped_steps = self._state[24:32].view(torch.int64)[0]
+        self._growth_interval, self._scale_set = growth_interval, False
+        self._write_scale(float(init_scale) if init_scale is not None else 1.0)
+        self._scale_set = init_scale is not None or not self.dynamic
+        self._ranges, at = [], 0
+        for key in self.heads:
+            nw, nb = sizes[key]
+            self._ranges.append((at, nw, at + nw, nb))
+            at += nw + nb
+        self._table = torch.zeros(len(self.heads) * C.sizeof(_lib.HeadUpdateDesc), dtype=torch.uint8, device=dev)
+        self._table_ptrs = None
+        self._update_ws = torch.empty(int(L.pp_head_update_workspace_bytes(self._flat.numel())), dtype=torch.uint8, device=dev)
+
+    def _write_scale(self, scale):
+        """(re)starts the state block at `scale`: good_steps 0, the skip count kept"""
+        import torch
+        from . import _lib
+        st = np.zeros(1, _lib.HEAD_UPDATE_STATE_DTYPE)
+        st["scale"], st["inv_scale"], st["growth_interval"] = scale, 1.0 / scale, self._growth_interval
+        st["min_scale"], st["max_scale"] = 2.0 ** -24, 2.0 ** 24
+        skipped = self.skipped_steps.clone()
+        self._state.copy_(torch.from_numpy(st.view(np.uint8)))
+        self.skipped_steps.copy_(skipped)
+        self._scale_set = True
+
+    def _sync_table(self):
+        """the device table of pp_head_update_f32 names the heads' fp16 tensors where they lie now (a layer re-lays its weight at its
+        first forward): rewritten, in place, when one moved -- never inside a capture"""
+        import torch
+        from . import _lib
+        ptrs = tuple((h.weight.data_ptr(), h.bias.data_ptr(), h.wpad.data_ptr(), h.bpad.data_ptr()) for h in self.heads.values())
+        if ptrs == self._table_ptrs:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise PosePafError("a head's fp16 tensor moved after the eager step: the captured update would write the old one")
+        table = (_lib.HeadUpdateDesc * len(ptrs))()
+        for d, head, (w_off, w_len, b_off, b_len), (pw, pb, pwp, pbp) in zip(table, self.heads.values(), self._ranges, ptrs):
+            k = head.k_real
+            for t, n in ((head.weight, w_len), (head.bias, b_len), (head.wpad[:k], w_len), (head.bpad[:k], b_len)):
+                dense = t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
+                if t.dtype != torch.float16 or t.numel() != n or not dense or tuple(t.shape[2:]) not in ((), (1, 1)):
+                    raise PosePafError("a head's fp16 tensor is not the dense binary16 image of its master")
+            d.w_off, d.w_len, d.b_off, d.b_len, d.weight, d.bias, d.wpad, d.bpad = w_off, w_len, b_off, b_len, pw, pb, pwp, pbp
+        self._table.copy_(torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()))
+        self._table_ptrs = ptrs
+
+    def _device_update(self):
+        import torch
+        from . import _lib
+        self._sync_table()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(_lib.load().pp_head_update_f32(ptr(self._flat), ptr(self._flat_grad), ptr(self._flat_buf), self._flat.numel(),
+                                                  ptr(self._table), len(self.heads), ptr(self._hyper), ptr(self._state), ptr(self._update_ws),
+                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def _check_inputs(self, x, target, mask):
         import torch
@@ -175,6 +304,14 @@ class HeadTrainer:
         g2 = torch.as_strided(g, (B * h * w, grad.shape[1]), (ldg, 1), g.storage_offset())
         return g2, ldg, x2, scale
 
+    def _grow_workspace(self, need):
+        """the weight gradients' workspace, replaced by a larger one when a call needs more.  A captured graph holds the address of
+        the one it was captured with: its entry in _graphs keeps that tensor alive (_graphed_step), so a replacement here never
+        returns memory that a later replay still writes"""
+        import torch
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+
     def _wgrad(self, key, g2, ldg, x2, scale, inv):
         import torch
         from . import _lib
@@ -191,32 +328,67 @@ class HeadTrainer:
         need = int(L.pp_head_wgrad_workspace_bytes(m, c_in, k))
         if need < 0:
             _lib.check(need)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._grow_workspace(need)
         _lib.check(L.pp_head_wgrad_f16(C.c_void_p(g2.data_ptr()), ldg, C.c_void_p(x2.data_ptr()),
                                        C.c_void_p(scale.data_ptr()) if scale is not None else None, m, hw, c_in, k, inv,
                                        C.c_void_p(self._workspace.data_ptr()), need, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()),
                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _wgrad_multi(self, inv):
+        """every head of last_inputs in one pp_head_wgrad_multi_f16 call; inv: a host float or the device float of the state block"""
+        import torch
+        from . import _lib
+        L = _lib.load()
+        table = (_lib.HeadWgradDesc * len(self.last_inputs))()
+        for d, (key, (g2, ldg, x2, scale)) in zip(table, self.last_inputs.items()):
+            dw, db = self._grads[key]
+            m, c_in = x2.shape
+            d.g, d.ldg, d.x, d.scale = g2.data_ptr(), ldg, x2.data_ptr(), scale.data_ptr() if scale is not None else None
+            d.m, d.hw, d.c_in, d.c_out = m, m // (scale.shape[0] if scale is not None else 1), c_in, g2.shape[1]
+            d.dw, d.db = dw.data_ptr(), db.data_ptr()
+        need = int(L.pp_head_wgrad_multi_workspace_bytes(len(table), table))
+        if need < 0:
+            _lib.check(need)
+        self._grow_workspace(need)
+        on_device = isinstance(inv, torch.Tensor)
+        _lib.check(L.pp_head_wgrad_multi_f16(len(table), table, 1.0 if on_device else inv, C.c_void_p(inv.data_ptr()) if on_device else None,
+                                             C.c_void_p(self._workspace.data_ptr()), need,
+                                             C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _scales(self, B):
+        """(what the term weights are multiplied by, what the sums are multiplied by): host floats, or with the dynamic scale the two
+        device floats of the state block"""
+        if not self.dynamic:
+            S = self.loss_scale_for(B)
+            return S, 1.0 / S
+        if not self._scale_set:
+            self._write_scale(auto_loss_scale(B, self.T, self.K, self.nstack_weight))
+        return self._scale, self._inv_scale
 
     def _backward(self, x, target, mask):
         """forward, loss terms, scaled loss gradient, every head's dw / db into the masters' .grad -> the unscaled loss"""
         import torch
         self._check_inputs(x, target, mask)
         B = x.shape[0]
-        S = self.loss_scale_for(B)
+        S, inv = self._scales(B)
         self._last_batch = B
+        if B not in self._tw:
+            self._tw[B] = torch.tensor(term_weights(B, self.T, self.K, self.nstack_weight), dtype=torch.float64, device=self.device)
         with torch.no_grad(), torch.cuda.device(self.device):
             self._seen.clear()
             preds = self.model(x.half() if x.dtype != torch.float16 else x, all_preds=True)
             terms = val_loss.focal_l2_terms(preds, target, mask=mask)
-            loss = val_loss.combine(terms, self.nstack_weight)
-            tw = torch.tensor(term_weights(B, self.T, self.K, self.nstack_weight), dtype=torch.float64, device=self.device)[:, :, None].expand(self.T, self.K, B)
-            grads = val_loss.focal_l2_grad(preds, target, (tw * S).contiguous(), mask)
+            loss = val_loss.combine(terms, self._nw, self._sw)
+            tw = self._tw[B][:, :, None].expand(self.T, self.K, B)
+            grads = val_loss.focal_l2_grad(preds, target, (tw * S).contiguous(), mask)       # a power of two: exact
             self.last_inputs = {}
             for key in self.heads:
                 g2, ldg, x2, scale = self._head_inputs(key, grads[key[0]][key[1]])
                 self.last_inputs[key] = (g2, ldg, x2, scale)
-                self._wgrad(key, g2, ldg, x2, scale, 1.0 / S)
+                if self.wgrad != "multi":
+                    self._wgrad(key, g2, ldg, x2, scale, inv)
+            if self.wgrad == "multi":
+                self._wgrad_multi(inv)
             self._seen.clear()
         return loss
 
@@ -242,21 +414,66 @@ class HeadTrainer:
         """dw / db once more from last_inputs -- the tensors the last gradients() / step() captured, no forward -- in the named
         formulation ("device" or "torch"), for A/B on identical inputs -> the dictionary gradients() returns"""
         import torch
-        if wgrad not in ("device", "torch") or not self.last_inputs:
-            raise PosePafError("gradients_from_last needs 'device' or 'torch' and a previous gradients() or step()")
-        S = self.loss_scale_for(self._last_batch)
+        if wgrad not in ("device", "torch", "multi") or not self.last_inputs:
+            raise PosePafError("gradients_from_last needs 'device', 'multi' or 'torch' and a previous gradients() or step()")
+        if self.dynamic and wgrad == "device":
+            raise PosePafError("loss_scale='dynamic': pp_head_wgrad_f16 takes its factor from the host, use 'multi' or 'torch'")
+        inv = self._scales(self._last_batch)[1]       # (dynamic: the scale as it is NOW, which a step since may have moved)
         keep, self.wgrad = self.wgrad, wgrad
         try:
             with torch.no_grad(), torch.cuda.device(self.device):
-                for key, (g2, ldg, x2, scale) in self.last_inputs.items():
-                    self._wgrad(key, g2, ldg, x2, scale, 1.0 / S)
+                if wgrad == "multi":
+                    self._wgrad_multi(inv)
+                else:
+                    for key, (g2, ldg, x2, scale) in self.last_inputs.items():
+                        self._wgrad(key, g2, ldg, x2, scale, inv)
         finally:
             self.wgrad = keep
         return {key: (dw.detach().clone().view(dw.shape[0], -1), db.detach().clone()) for key, (dw, db) in self._grads.items()}
 
     def step(self, x, target, mask=None):
+        """one training step -> the unscaled loss, a 0-d float64 device tensor; asynchronous"""
+        if self.graph:
+            return self._graphed_step(x, target, mask)
+        return self._step(x, target, mask)
+
+    def _graphed_step(self, x, target, mask):
+        """the first call of a signature: eager.  The second: capture over static copies of the inputs, then as every later one:
+        copy the inputs in, replay, return a copy of the graph's loss scalar"""
         import torch
+        self._check_inputs(x, target, mask)
+        sig = (tuple(x.shape), x.dtype, tuple(target.shape), target.dtype, mask is not None)
+        entry = self._graphs.get(sig)
+        if entry is None:
+            self._graphs[sig] = "seen"
+            return self._step(x, target, mask)
+        with torch.cuda.device(self.device):
+            if entry == "seen":
+                sx, st, sm = x.clone(), target.clone(), mask.clone() if mask is not None else None
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    loss = self._step(sx, st, sm)
+                # the last element pins what the graph addresses beyond its own pool: the workspace of this capture, which a
+                # later, larger eager call (another signature, gradients(), gradients_from_last("multi")) replaces in self
+                entry = self._graphs[sig] = (graph, sx, st, sm, loss, self._workspace)
+            graph, sx, st, sm, loss = entry[:5]
+            sx.copy_(x), st.copy_(target)
+            if sm is not None:
+                sm.copy_(mask)
+            graph.replay()
+            self.graph_replays += 1
+            return loss.clone()
+
+    def _step(self, x, target, mask):
         loss = self._backward(x, target, mask)
+        if self.update == "device":
+            self._device_update()
+        else:
+            self._torch_update()
+        return loss
+
+    def _torch_update(self):
+        import torch
         with torch.no_grad():
             finite = torch.isfinite(self._flat_grad).all()
             old, old_buf = self._flat.clone(), self._flat_buf.clone()
@@ -266,7 +483,6 @@ class HeadTrainer:
             self._flat_buf.copy_(torch.where(finite, self._flat_buf, old_buf))
             self.skipped_steps += (~finite).to(torch.int64)
         self._push_masters()
-        return loss
 
     def grad_norm(self):
         """the L2 norm of the heads' gradients of the last gradients() / step() -> 0-d float64 device tensor"""

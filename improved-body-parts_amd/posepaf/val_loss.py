@@ -157,7 +157,10 @@ def _terms(shape, preds, target, mask, multi_task_weight, keypoint_task_weight, 
                 PP_F16 if target.dtype == torch.float16 else PP_F32, image_stride, C.c_void_p(mask.data_ptr()) if mask is not None else None,
                 B, H, W, T, k, hs, ws, float(multi_task_weight), float(keypoint_task_weight), flags, C.c_void_p(workspace.data_ptr()),
                 C.c_void_p(dst.data_ptr()), C.c_void_p(st.cuda_stream)))
-            if not whole:
+            if not whole and torch.cuda.is_current_stream_capturing():
+                for j, s in enumerate(members):        # (an index list is a host tensor the capture could not transfer)
+                    out[:, s].copy_(dst[:, j])
+            elif not whole:
                 out[:, members] = dst
     return out
 
@@ -226,7 +229,12 @@ def focal_l2_grad(preds, target, term_weights, mask=None, multi_task_weight: flo
                             if stride > sk.NUM_CH:
                                 buf[..., sk.NUM_CH:].zero_()
                             grads[t][s] = buf.permute(0, 3, 1, 2)[:, :sk.NUM_CH]
-                part = tw if k == K else tw[:, members].contiguous()
+                if k == K:
+                    part = tw
+                elif torch.cuda.is_current_stream_capturing():     # as in _terms: no index list inside a capture
+                    part = torch.stack([tw[:, s] for s in members], dim=1)
+                else:
+                    part = tw[:, members].contiguous()
                 table = (C.c_void_p * (T * k))(*[keep[s][t].data_ptr() for t in range(T) for s in members])
                 gtable = (C.c_void_p * (T * k))(*[grads[t][s].data_ptr() for t in range(T) for s in members])
                 hs, ws = (C.c_int * k)(*[sizes[s][0] for s in members]), (C.c_int * k)(*[sizes[s][1] for s in members])
@@ -276,6 +284,10 @@ def _weights(values, n, name, ref):
     import torch
     if len(values) < n:
         raise PosePafError(f"{name} has {len(values)} entries, the terms hold {n}")
+    if isinstance(values, torch.Tensor):       # the caller's own device copy: no transfer here (a stream capture allows none)
+        if values.dim() != 1 or values.dtype != torch.float64 or values.device != ref.device:
+            raise PosePafError(f"{name} as a tensor must be 1-D float64 on {ref.device}")
+        return values[:n]
     return torch.tensor([float(v) for v in values[:n]], dtype=torch.float64, device=ref.device)
 
 

@@ -761,6 +761,72 @@ PP_API long long pp_head_wgrad_workspace_bytes(long m, int c_in, int c_out);
 PP_API int pp_head_wgrad_f16(const void *g, int ldg, const void *x, const void *scale, long m, int hw, int c_in, int c_out,
                              float inv_loss_scale, void *workspace, long long workspace_bytes, float *dw, float *db, void *stream);
 
+/* Every head of a training step in one call.  A descriptor holds the per-head arguments of pp_head_wgrad_f16, and for every head dw
+ * and db are BIT-EQUAL to what that entry stores for the same arguments, at every shape, alignment and row pitch it accepts: a head
+ * keeps its own min(256, ceil(m / 64)) workgroups, their chunks, the four-run reduction order and the exact products; only the
+ * launches are shared.  At most one accumulate launch per distinct (c_in, 16-byte / element load of g) pair among the heads, then
+ * one finishing launch for all of them; the descriptors travel in the kernel arguments, so a graph capture freezes them.
+ *   inv_loss_scale_dev  NULL: the finishing launch multiplies by the host's inv_loss_scale.  Else a DEVICE float the finishing
+ *                       launch reads when it runs (the host value is ignored): a captured step whose loss scale moves
+ *   workspace           DEVICE, at least pp_head_wgrad_multi_workspace_bytes (the sum of the heads' own sizes, a slice per head in
+ *                       table order); never assumed zero, no memset, no atomics; nothing outside every dw and db is written
+ * Asynchronous, allocates nothing, needs no pp_ctx, capturable.
+ * Refusals (nothing launched, outputs untouched), in this order:  PP_ERR_BAD_ARG: a null table or n_heads <= 0.
+ * PP_ERR_UNSUPPORTED: n_heads > pp_head_wgrad_multi_max_heads().  Then, head by head, the first refusal of pp_head_wgrad_f16's list
+ * that concerns a descriptor's own fields (null g, x, dw, db; m, hw; ldg; alignment of g, x, scale, dw, db; unsupported; too large).
+ * PP_ERR_BAD_ARG: a workspace that is null, off a 4-byte boundary or too small.  PP_ERR_BAD_ARG: inv_loss_scale_dev off a 4-byte
+ * boundary; with a NULL inv_loss_scale_dev, an inv_loss_scale that is not finite and positive.  PP_ERR_NO_DEVICE after those. */
+#define PP_HEAD_WGRAD_MULTI_MAX 40      /* the loss's 8 stacks x 5 scales */
+typedef struct {
+    const void *g;
+    int ldg;
+    const void *x;
+    const void *scale;
+    long m;
+    int hw, c_in, c_out;
+    float *dw;
+    float *db;
+} pp_head_wgrad_desc;
+PP_API int pp_head_wgrad_multi_max_heads(void);
+/* bytes, or the negative pp_status of the first refusal above up to the heads' own */
+PP_API long long pp_head_wgrad_multi_workspace_bytes(int n_heads, const pp_head_wgrad_desc *heads);
+PP_API int pp_head_wgrad_multi_f16(int n_heads, const pp_head_wgrad_desc *heads, float inv_loss_scale, const float *inv_loss_scale_dev,
+                                   void *workspace, long long workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------- the heads' optimiser step on the device (csrc/posepaf_headopt.hip)
+ * One chain of two launches: the finite test of all n gradients, then -- when every one is finite -- torch.optim.SGD's update
+ * (dampening 0, no Nesterov) of the float32 masters, their binary16 copies, and the loss-scale state machine.
+ *   g' = fma(wd, p, g)  (wd = 0: g' = g);   buf' = fl(mu * buf) + g'  (mu = 0: no buffer is read or written, buf' = g');
+ *   p' = fma(-lr, buf', p)                  -- each operation rounded where this torch build's SGD kernels round it
+ *   masters, momentum   DEVICE float32 (n), updated in place;  grads  DEVICE float32 (n), read only
+ *   table      DEVICE pp_head_update_desc[n_heads]: where a head's weight and bias lie in the flat tensors and the four binary16
+ *              destinations of their nearest-even roundings: weight and wpad receive w_len elements from w_off, bias and bpad b_len
+ *              from b_off (the first rows of the zero-padded copies; the rows behind are never touched).  Ranges in ascending
+ *              order, disjoint, inside [0, n); an element of no range is updated and copied nowhere
+ *   hyper      DEVICE float[3] = lr, momentum, weight_decay (read when the launch runs: a schedule needs no new capture)
+ *   state      DEVICE pp_head_update_state.  A non-finite gradient: masters, momentum and every binary16 copy keep their bits,
+ *              skipped += 1, scale = max(scale / 2, min_scale), good_steps = 0.  A finite step: good_steps += 1, and when it reaches
+ *              growth_interval: scale = min(2 scale, max_scale), good_steps = 0.  inv_scale = 1 / scale.  growth_interval = 0: static,
+ *              scale, inv_scale and good_steps never move (skipped still counts)
+ *   workspace  DEVICE, pp_head_update_workspace_bytes(n): one flag word per workgroup of the first launch, stored with plain
+ *              stores on every call and OR-ed by the second; no memset, no atomics
+ * Asynchronous, allocates nothing, needs no pp_ctx, capturable.  Refusals before any launch: PP_ERR_BAD_ARG for a null pointer,
+ * n <= 0, n_heads < 0, masters / grads / momentum / hyper / workspace off a 4-byte boundary, table / state off an 8-byte one;
+ * PP_ERR_UNSUPPORTED for n_heads > pp_head_wgrad_multi_max_heads(); PP_ERR_TOO_LARGE for n > 2^31 - 1; PP_ERR_NO_DEVICE last. */
+typedef struct {
+    long long w_off, w_len, b_off, b_len;
+    void *weight, *bias, *wpad, *bpad;
+} pp_head_update_desc;
+typedef struct {
+    float scale, inv_scale;
+    int good_steps, growth_interval;
+    float min_scale, max_scale;
+    long long skipped;
+} pp_head_update_state;
+PP_API long long pp_head_update_workspace_bytes(long n);
+PP_API int pp_head_update_f32(float *masters, const float *grads, float *momentum, long n, const pp_head_update_desc *table, int n_heads,
+                              const float *hyper, pp_head_update_state *state, void *workspace, void *stream);
+
 /* ---------------------------------------------------------------- Python twins, host form
  * utils.parse_skeletons.find_connections / find_humans (:324-600) with host arrays, for callers of the non --run_cpp
  * branch of evaluate.py (:88-89).  peaks: joint-list rows [x, y, score, id, part] (n of them); paf: (H, W, C) float32.
