@@ -53,6 +53,9 @@ evaluate.py -p loads); val_loss.focal_l2_terms -> combine -> backward() (pp_foca
                   --graph (implies --update device): the first step eager, the second captured into one graph, the rest replayed, the
                   losses read once after the last step.  The JSON line gains "graph", "update",
                   "graph_replays" and "loss_scale_last"
+  --train heads+conv (with --model fused --arch final | auto) the 3 x 3 convolution in front of every head is trained as well:
+                  pp_head_dgrad_f16 and pp_conv3x3_wgrad_f16 per layer, float32 masters of the folded weight and bias in the same
+                  flat tensors, update, scale and capture as the heads
 
 Prints one JSON line: losses (per step), loss_first, loss_last, grad_norm_first (L2 norm of the updated parameters' gradients at
 step 0), seconds, steps_per_s (steady state: from the second step on, with --graph from the third, so without the first step's set-up
@@ -84,7 +87,8 @@ def parse(argv=None):
     ap.add_argument("--sizes", default="128x128", help="image size HxW: one size, both sides multiples of 64")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--stages", type=int, default=4, help="hourglass stages of the network (a checkpoint must hold as many)")
-    ap.add_argument("--train", choices=("all", "heads"), default="all")
+    ap.add_argument("--train", choices=("all", "heads", "heads+conv"), default="all",
+                    help="heads+conv (with --model fused --arch final | auto): the 3 x 3 convolution in front of every head as well")
     ap.add_argument("--lr", type=float, default=2.5e-5)
     ap.add_argument("--loss", choices=("device", "torch"), default="device")
     ap.add_argument("-p", "--checkpoint_path", default=None)
@@ -151,8 +155,11 @@ def refusals(a):
         out.append("--batch and --steps must be at least 1")
     if a.model == "fused":
         from posepaf.head_train import is_power_of_two
-        if a.train != "heads":
-            out.append("--model fused trains the heads only (the fused model has no backward): pass --train heads")
+        if a.train not in ("heads", "heads+conv"):
+            out.append("--model fused trains the heads, or with --train heads+conv the convolution in front of each as well (the fused "
+                       "model has no other backward): pass --train heads or --train heads+conv")
+        if a.train == "heads+conv" and a.arch not in ("final", "auto"):
+            out.append("--train heads+conv needs --arch final (or auto): on posenet an SE block stands between the convolution and the head")
         if a.loss != "device":
             out.append("--model fused takes the loss gradient from pp_focal_l2_grad: --loss torch belongs to --model plain")
         if a.loss_scale not in ("auto", "dynamic") and not is_power_of_two(a.loss_scale):
@@ -166,6 +173,8 @@ def refusals(a):
             out.append("--growth_interval must be at least 0")
         elif a.growth_given and a.loss_scale != "dynamic":
             out.append("--growth_interval belongs to --loss_scale dynamic")
+    elif a.train == "heads+conv":
+        out.append("--train heads+conv belongs to --model fused (--arch final | auto)")
     elif a.arch != "posenet" or a.loss_scale != "auto" or a.wgrad != "device" or a.graph or a.update_given or a.growth_given:
         out.append("--arch, --loss_scale, --wgrad, --update, --graph and --growth_interval belong to --model fused")
     sizes = a.sizes.split(",")
@@ -361,7 +370,7 @@ def main(argv=None):
         try:
             tr = head_train.HeadTrainer(net, dev, lr=a.lr, momentum=MOMENTUM, weight_decay=WEIGHT_DECAY, wgrad=a.wgrad,
                                         loss_scale=a.loss_scale if a.loss_scale in ("auto", "dynamic") else float(a.loss_scale),
-                                        update=a.update, graph=a.graph, growth_interval=a.growth_interval)
+                                        update=a.update, graph=a.graph, growth_interval=a.growth_interval, train=a.train)
         except _lib.PosePafError as e:
             raise SystemExit(f"finetune.py: --model fused: {e}")
         a.stages = tr.T

@@ -49,6 +49,8 @@ EXPORTS = [
     "pp_head_wgrad_supported", "pp_head_wgrad_chunk_pixels", "pp_head_wgrad_max_workgroups", "pp_head_wgrad_workspace_bytes",
     "pp_head_wgrad_f16", "pp_head_wgrad_multi_max_heads", "pp_head_wgrad_multi_workspace_bytes", "pp_head_wgrad_multi_f16",
     "pp_head_update_workspace_bytes", "pp_head_update_f32",
+    "pp_head_dgrad_supported", "pp_head_dgrad_f16", "pp_conv3x3_wgrad_supported", "pp_conv3x3_wgrad_max_workgroups",
+    "pp_conv3x3_wgrad_workspace_bytes", "pp_conv3x3_wgrad_f16",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -171,6 +173,13 @@ def load():
     L.pp_head_update_workspace_bytes.argtypes = [C.c_long]
     L.pp_head_update_workspace_bytes.restype = C.c_longlong
     L.pp_head_update_f32.argtypes = [vp, vp, vp, C.c_long, vp, C.c_int, vp, vp, vp, vp]
+    L.pp_head_dgrad_supported.argtypes = [C.c_int, C.c_int]
+    L.pp_head_dgrad_f16.argtypes = [vp, C.c_int, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, vp, vp]
+    L.pp_conv3x3_wgrad_supported.argtypes = [C.c_int, C.c_int]
+    L.pp_conv3x3_wgrad_max_workgroups.argtypes = []
+    L.pp_conv3x3_wgrad_workspace_bytes.argtypes = [C.c_int] * 5
+    L.pp_conv3x3_wgrad_workspace_bytes.restype = C.c_longlong
+    L.pp_conv3x3_wgrad_f16.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_longlong, vp, vp, vp]
     L.pp_flip_average.argtypes =[vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_pwconv_supported.argtypes = [C.c_int, C.c_int]
     L.pp_pwconv_f16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int, vp]

@@ -38,6 +38,16 @@ step() of a signature -- (shape and dtype of x, shape and dtype of target, mask 
 candidates there), the second captures forward, loss, gradients and update into one torch.cuda.CUDAGraph over static copies of the
 inputs and replays it, later ones copy the inputs in and replay: the same bits as graph=False, step for step.  graph=True sets
 torch.backends.cudnn.deterministic (the few MIOpen layers must add in one order for that to hold).
+
+train="heads+conv" (the 'final' architecture only: on 'posenet' an SE block stands in between).  The 3 x 3
+convolution in front of every head (features[t].before_regress[s][2]: conv, frozen BN, LeakyReLU) is trained as well.  Its masters are
+the weight and bias with the BN FOLDED in float32 (fused_model._fold of the plain layer), the weight in (K, 3, 3, C) order -- the memory
+of the fused layer's channels-last binary16 tensor, which receives the rounded master in place.  Per layer, after the heads:
+pp_head_dgrad_f16 takes the loss gradient through the head's current binary16 weight and the activation (dY, binary16),
+pp_conv3x3_wgrad_f16 forms dw / db from dY and the convolution's captured input with the heads' loss-scale factor.  wgrad="torch"
+forms both in float64 with the contract's roundings.  The same flat tensors, finite test, update paths, dynamic scale and capture
+cover them.  gradients() returns them under ("conv", t, s); state_dict() writes the folded master as the plain convolution's weight
+behind a BN whose fold is exact (identity_bn_var), so a model rebuilt from it runs the trainer's binary16 bits.
 """
 import ctypes as C
 import math
@@ -75,6 +85,21 @@ def is_power_of_two(v) -> bool:
     return math.isfinite(v) and v > 0 and math.frexp(v)[0] == 0.5 and 2.0 ** -24 <= v <= 2.0 ** 24
 
 
+def identity_bn_var(eps):
+    """a float32 running_var v next to 1 - eps with sqrt(fl32(v + eps)) == 1.0f: with running_mean 0 and weight 1, fused_model._fold
+    then multiplies the convolution's weight by exactly 1 and returns the BN bias as the folded bias, bit for bit"""
+    import torch
+    v = np.float32(1.0) - np.float32(eps)
+    candidates, up, down = [v], v, v
+    for _ in range(8):              # the nearest first
+        up, down = np.nextafter(up, np.float32(2.0)), np.nextafter(down, np.float32(0.0))
+        candidates += [up, down]
+    for c in (float(c) for c in candidates):
+        if float(torch.sqrt(torch.tensor(c, dtype=torch.float32) + eps)) == 1.0:
+            return c
+    raise PosePafError(f"no float32 running_var folds to the identity with eps = {eps!r}")
+
+
 def _pixel_major(grad):
     """a (B, 50, h, w) gradient as (tensor whose data_ptr is pixel 0, ldg): in place where it is pixel-major with one pixel stride"""
     B, k, h, w = grad.shape
@@ -89,7 +114,7 @@ def _pixel_major(grad):
 
 class HeadTrainer:
     def __init__(self, net, device, lr=2.5e-5, momentum=0.9, weight_decay=1e-4, loss_scale="auto", wgrad="device", arch=None,
-                 update="torch", graph=False, growth_interval=2000, init_scale=None):
+                 update="torch", graph=False, growth_interval=2000, init_scale=None, train="heads"):
         import torch
         from . import fused_model
         pn = getattr(net, "posenet", None)
@@ -124,6 +149,11 @@ class HeadTrainer:
         found = "final" if isinstance(pn, posenet_final.PoseNet) else "posenet"
         if arch not in (None, found):
             raise PosePafError(f"arch = {arch!r}, the network is {found!r}")
+        if train not in ("heads", "heads+conv"):
+            raise PosePafError(f"train = {train!r}: 'heads' or 'heads+conv' (the 3 x 3 convolution in front of every head as well)")
+        if train == "heads+conv" and found != "final":
+            raise PosePafError("train='heads+conv' needs the 'final' architecture: on 'posenet' an SE block stands between the "
+                               "convolution and the head, and it has no backward here")
         for t, stage in enumerate(pn.outs):
             for s, c in enumerate(stage):
                 if c.bn is not None or c.relu is not None or tuple(c.conv.kernel_size) != (1, 1) or c.conv.bias is None:
@@ -138,20 +168,25 @@ class HeadTrainer:
         self.heads = {(t, s): self.model.head[t][s] for t in range(self.T) for s in range(self.K)}
         # the reference's configuration weighs its four stages alike; a deeper stack keeps doing so
         self.nstack_weight = tuple(val_loss.NSTACK_WEIGHT) + (1,) * max(0, self.T - len(val_loss.NSTACK_WEIGHT))
+        self.train, self.convs = train, {}
         # float32 masters, their gradients and momentum buffers as views of three flat tensors: one finite test, one masked restore
-        sizes = {}
+        sources = {}
         for key in self.heads:
             conv = pn.outs[key[0]][key[1]].conv
-            sizes[key] = (conv.weight.numel(), conv.bias.numel())
+            sources[key] = (conv.weight.detach(), conv.bias.detach())
+        if train == "heads+conv":       # behind the heads, so that their ranges are those of train='heads'
+            for t, s in self.heads:
+                sources[("conv", t, s)] = self._conv_source(pn, t, s)
+                self.convs[("conv", t, s)] = self.model.feat[t][s].c3
+        sizes = {key: (w.numel(), b.numel()) for key, (w, b) in sources.items()}
         total = sum(a + b for a, b in sizes.values())
         self._flat = torch.empty(total, dtype=torch.float32, device=device)
         self._flat_grad = torch.zeros(total, dtype=torch.float32, device=device)
         self._flat_buf = torch.zeros(total, dtype=torch.float32, device=device)
         self.masters, self._grads, params, at = {}, {}, [], 0
         for key, (nw, nb) in sizes.items():
-            conv = pn.outs[key[0]][key[1]].conv
             pair, gpair = [], []
-            for n, src in ((nw, conv.weight), (nb, conv.bias)):
+            for n, src in zip((nw, nb), sources[key]):
                 view = self._flat[at:at + n].view(src.shape)
                 view.copy_(src.detach().float())
                 p = torch.nn.Parameter(view, requires_grad=True)
@@ -170,9 +205,28 @@ class HeadTrainer:
         self._sw = torch.tensor([float(v) for v in val_loss.SCALE_WEIGHT[:self.K]], dtype=torch.float64, device=device)
         if update == "device":
             self._init_device_update(sizes, lr, momentum, weight_decay, growth_interval if dynamic else 0, init_scale if dynamic else None)
-        for key, head in self.heads.items():
-            head.register_forward_pre_hook(lambda mod, args, key=key: self._seen.__setitem__(key, args[0]))
+        for key, layer in list(self.heads.items()) + list(self.convs.items()):
+            layer.register_forward_pre_hook(lambda mod, args, key=key: self._seen.__setitem__(key, args[0]))
         self._push_masters()
+
+    def _conv_source(self, pn, t, s):
+        """(weight (K, 3, 3, C), bias (K,)) float32 of before_regress[s][2] of stage t with its BN folded in float32 (fused_model._fold on
+        the plain layer, not the fused model's binary16 copy), the weight in the memory order of the fused layer's channels-last tensor"""
+        import torch
+        from . import _lib, fused_model
+        blk = pn.features[t].before_regress[s][2]
+        c3, conv = self.model.feat[t][s].c3, blk.conv
+        plain = (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups)
+        if plain != ((3, 3), (1, 1), (1, 1), (1, 1), 1) or blk.relu is None or not c3.act:
+            raise PosePafError(f"before_regress[{s}][2] of stage {t} is not a 3 x 3 / pad 1 / stride 1 convolution with a LeakyReLU")
+        k, c = conv.weight.shape[:2]
+        L = _lib.load()
+        if not L.pp_conv3x3_wgrad_supported(c, k) or not L.pp_head_dgrad_supported(k, self.heads[(t, s)].k_real):
+            raise PosePafError(f"before_regress[{s}][2] of stage {t}: {c} -> {k} channels are outside the gradient kernels' shapes")
+        if c3.weight.dtype != torch.float16 or not c3.weight.is_contiguous(memory_format=torch.channels_last):
+            raise PosePafError("the fused 3 x 3 layer does not keep its weight as one channels-last binary16 tensor")
+        w, b = fused_model._fold(conv, blk.bn)
+        return w.permute(0, 2, 3, 1).contiguous(), b
 
     # ---- pieces of a step
 
@@ -211,8 +265,8 @@ class HeadTrainer:
         import torch
         from . import _lib
         L = _lib.load()
-        if len(self.heads) > L.pp_head_wgrad_multi_max_heads():
-            raise PosePafError(f"{len(self.heads)} heads: pp_head_update_f32 takes {L.pp_head_wgrad_multi_max_heads()}")
+        if len(sizes) > L.pp_head_wgrad_multi_max_heads():
+            raise PosePafError(f"{len(sizes)} trained layers: pp_head_update_f32 takes {L.pp_head_wgrad_multi_max_heads()}")
         dev = self.device
         self._hyper = torch.tensor([lr, momentum, weight_decay], dtype=torch.float32, device=dev)
         self._state = torch.zeros(_lib.HEAD_UPDATE_STATE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
@@ -223,11 +277,11 @@ class HeadTrainer:
         self._write_scale(float(init_scale) if init_scale is not None else 1.0)
         self._scale_set = init_scale is not None or not self.dynamic
         self._ranges, at = [], 0
-        for key in self.heads:
+        for key in sizes:               # the heads, then the convolutions: the order of the flat tensors
             nw, nb = sizes[key]
             self._ranges.append((at, nw, at + nw, nb))
             at += nw + nb
-        self._table = torch.zeros(len(self.heads) * C.sizeof(_lib.HeadUpdateDesc), dtype=torch.uint8, device=dev)
+        self._table = torch.zeros(len(sizes) * C.sizeof(_lib.HeadUpdateDesc), dtype=torch.uint8, device=dev)
         self._table_ptrs = None
         self._update_ws = torch.empty(int(L.pp_head_update_workspace_bytes(self._flat.numel())), dtype=torch.uint8, device=dev)
 
@@ -248,18 +302,28 @@ class HeadTrainer:
         first forward): rewritten, in place, when one moved -- never inside a capture"""
         import torch
         from . import _lib
+        # a convolution has no padded copies: its descriptor names the weight and the bias twice, and the second store of an element
+        # writes the value the first one wrote
         ptrs = tuple((h.weight.data_ptr(), h.bias.data_ptr(), h.wpad.data_ptr(), h.bpad.data_ptr()) for h in self.heads.values())
+        ptrs += tuple((c.weight.data_ptr(), c.bias.data_ptr()) * 2 for c in self.convs.values())
         if ptrs == self._table_ptrs:
             return
         if torch.cuda.is_current_stream_capturing():
             raise PosePafError("a head's fp16 tensor moved after the eager step: the captured update would write the old one")
         table = (_lib.HeadUpdateDesc * len(ptrs))()
-        for d, head, (w_off, w_len, b_off, b_len), (pw, pb, pwp, pbp) in zip(table, self.heads.values(), self._ranges, ptrs):
-            k = head.k_real
-            for t, n in ((head.weight, w_len), (head.bias, b_len), (head.wpad[:k], w_len), (head.bpad[:k], b_len)):
-                dense = t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
-                if t.dtype != torch.float16 or t.numel() != n or not dense or tuple(t.shape[2:]) not in ((), (1, 1)):
-                    raise PosePafError("a head's fp16 tensor is not the dense binary16 image of its master")
+        layers = list(self.heads.values()) + list(self.convs.values())
+        for d, layer, (w_off, w_len, b_off, b_len), (pw, pb, pwp, pbp) in zip(table, layers, self._ranges, ptrs):
+            if hasattr(layer, "wpad"):
+                k = layer.k_real
+                for t, n in ((layer.weight, w_len), (layer.bias, b_len), (layer.wpad[:k], w_len), (layer.bpad[:k], b_len)):
+                    dense = t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
+                    if t.dtype != torch.float16 or t.numel() != n or not dense or tuple(t.shape[2:]) not in ((), (1, 1)):
+                        raise PosePafError("a head's fp16 tensor is not the dense binary16 image of its master")
+            else:       # (K, C, 3, 3) channels-last is the master's (K, 3, 3, C) element by element
+                w, b = layer.weight, layer.bias
+                if (w.dtype != torch.float16 or b.dtype != torch.float16 or w.numel() != w_len or b.numel() != b_len
+                        or not w.is_contiguous(memory_format=torch.channels_last) or not b.is_contiguous()):
+                    raise PosePafError("a convolution's fp16 tensor is not the dense binary16 image of its master")
             d.w_off, d.w_len, d.b_off, d.b_len, d.weight, d.bias, d.wpad, d.bpad = w_off, w_len, b_off, b_len, pw, pb, pwp, pbp
         self._table.copy_(torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()))
         self._table_ptrs = ptrs
@@ -270,7 +334,7 @@ class HeadTrainer:
         self._sync_table()
         ptr = lambda t: C.c_void_p(t.data_ptr())
         _lib.check(_lib.load().pp_head_update_f32(ptr(self._flat), ptr(self._flat_grad), ptr(self._flat_buf), self._flat.numel(),
-                                                  ptr(self._table), len(self.heads), ptr(self._hyper), ptr(self._state), ptr(self._update_ws),
+                                                  ptr(self._table), len(self.heads) + len(self.convs), ptr(self._hyper), ptr(self._state), ptr(self._update_ws),
                                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def _check_inputs(self, x, target, mask):
@@ -339,8 +403,9 @@ class HeadTrainer:
         import torch
         from . import _lib
         L = _lib.load()
-        table = (_lib.HeadWgradDesc * len(self.last_inputs))()
-        for d, (key, (g2, ldg, x2, scale)) in zip(table, self.last_inputs.items()):
+        table = (_lib.HeadWgradDesc * len(self.heads))()
+        for d, key in zip(table, self.heads):
+            g2, ldg, x2, scale = self.last_inputs[key]
             dw, db = self._grads[key]
             m, c_in = x2.shape
             d.g, d.ldg, d.x, d.scale = g2.data_ptr(), ldg, x2.data_ptr(), scale.data_ptr() if scale is not None else None
@@ -389,14 +454,62 @@ class HeadTrainer:
                     self._wgrad(key, g2, ldg, x2, scale, inv)
             if self.wgrad == "multi":
                 self._wgrad_multi(inv)
+            for key, c3 in self.convs.items():
+                head = self.heads[key[1:]]
+                self.last_inputs[key] = (head.weight.detach().reshape(head.k_real, -1).clone(),
+                                         self._seen[key].permute(0, 2, 3, 1).contiguous(), None)
+                self._conv_grads(key, inv, self.wgrad)
             self._seen.clear()
         return loss
+
+    def _conv_grads(self, key, inv, how):
+        """("conv", t, s): dY = the loss gradient through head (t, s) and the LeakyReLU in front of it, then the convolution's dw / db
+        into the masters' .grad, from last_inputs: the head's (g, ldg, y, None) and this key's (head weight, NHWC input, .); the third
+        element becomes dY.  how 'torch': both steps in float64 with the contract's roundings; else pp_head_dgrad_f16 and
+        pp_conv3x3_wgrad_f16.  inv: a host float or the device float of the state block"""
+        import torch
+        from . import _lib, fused_model
+        g2, ldg, y2, scale = self.last_inputs[key[1:]]
+        w16, x_in = self.last_inputs[key][:2]
+        dw, db = self._grads[key]
+        B, h, w, c_in = x_in.shape
+        m, c_mid = y2.shape
+        if scale is not None or m != B * h * w or tuple(dw.shape) != (c_mid, 3, 3, c_in):
+            raise PosePafError(f"{key}: the head's captured input is not this convolution's output")
+        if how == "torch":
+            s = g2.double() @ w16.double()
+            dy = torch.where(y2 > 0, s, float(np.float32(fused_model.LEAK)) * s).half()
+            d64 = dy.double()
+            g64 = torch.nn.grad.conv2d_weight(x_in.double().permute(0, 3, 1, 2), (c_mid, c_in, 3, 3),
+                                              d64.view(B, h, w, c_mid).permute(0, 3, 1, 2), stride=1, padding=1)
+            dw.copy_(g64.permute(0, 2, 3, 1).float() * inv)
+            db.copy_(d64.sum(dim=0).float() * inv)
+            self.last_inputs[key] = (w16, x_in, dy)
+            return
+        L = _lib.load()
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        dy = torch.empty((m, c_mid), dtype=torch.float16, device=self.device)
+        _lib.check(L.pp_head_dgrad_f16(C.c_void_p(g2.data_ptr()), ldg, C.c_void_p(w16.data_ptr()), C.c_void_p(y2.data_ptr()), m, c_mid,
+                                       g2.shape[1], fused_model.LEAK, C.c_void_p(dy.data_ptr()), stream))
+        need = int(L.pp_conv3x3_wgrad_workspace_bytes(B, h, w, c_in, c_mid))
+        if need < 0:
+            _lib.check(need)
+        self._grow_workspace(need)
+        on_device = isinstance(inv, torch.Tensor)
+        _lib.check(L.pp_conv3x3_wgrad_f16(C.c_void_p(dy.data_ptr()), C.c_void_p(x_in.data_ptr()), B, h, w, c_in, c_mid,
+                                          1.0 if on_device else inv, C.c_void_p(inv.data_ptr()) if on_device else None,
+                                          C.c_void_p(self._workspace.data_ptr()), need, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()),
+                                          stream))
+        self.last_inputs[key] = (w16, x_in, dy)
 
     def _push_masters(self):
         """the masters, rounded to binary16, in place into the fused heads' tensors"""
         import torch
         with torch.no_grad():
             for key, (w, b) in self.masters.items():
+                if key in self.convs:       # (K, 3, 3, C) into the channels-last (K, C, 3, 3): element by element, pointers stay
+                    self.convs[key].weight.copy_(w.permute(0, 3, 1, 2)), self.convs[key].bias.copy_(b)
+                    continue
                 head = self.heads[key]
                 k = head.k_real
                 head.weight.copy_(w), head.bias.copy_(b)
@@ -408,7 +521,14 @@ class HeadTrainer:
         """{(t, s): (dw float32 (50, c_in), db float32 (50,))} of the UNSCALED loss, copies; no update.  Keeps
         last_inputs[(t, s)] = (g, ldg, x, scale): what the head's pp_head_wgrad_f16 call read (g as a (m, 50) view with row stride ldg)"""
         self._backward(x, target, mask)
-        return {key: (dw.detach().clone().view(dw.shape[0], -1), db.detach().clone()) for key, (dw, db) in self._grads.items()}
+        return self._grad_copies()
+
+    def _grad_copies(self):
+        """a head's dw as (50, c_in); with train='heads+conv' also ("conv", t, s): (dw float32 (K, 3, 3, C), db float32 (K,)), and
+        last_inputs[("conv", t, s)] = (the head's binary16 weight (50, K), the convolution's NHWC input, dY (m, K)): what
+        pp_head_dgrad_f16 read besides the head's entry, and what pp_conv3x3_wgrad_f16 read"""
+        return {key: (dw.detach().clone() if key in self.convs else dw.detach().clone().view(dw.shape[0], -1), db.detach().clone())
+                for key, (dw, db) in self._grads.items()}
 
     def gradients_from_last(self, wgrad):
         """dw / db once more from last_inputs -- the tensors the last gradients() / step() captured, no forward -- in the named
@@ -425,11 +545,14 @@ class HeadTrainer:
                 if wgrad == "multi":
                     self._wgrad_multi(inv)
                 else:
-                    for key, (g2, ldg, x2, scale) in self.last_inputs.items():
+                    for key in self.heads:
+                        g2, ldg, x2, scale = self.last_inputs[key]
                         self._wgrad(key, g2, ldg, x2, scale, inv)
+                for key in self.convs:
+                    self._conv_grads(key, inv, wgrad)
         finally:
             self.wgrad = keep
-        return {key: (dw.detach().clone().view(dw.shape[0], -1), db.detach().clone()) for key, (dw, db) in self._grads.items()}
+        return self._grad_copies()
 
     def step(self, x, target, mask=None):
         """one training step -> the unscaled loss, a 0-d float64 device tensor; asynchronous"""
@@ -491,10 +614,26 @@ class HeadTrainer:
 
     def state_dict(self):
         """the plain network's state dict (its keys; tensors on their devices) with outs.* replaced by copies of the float32 masters"""
+        import torch
         sd = {k: v.detach() for k, v in self.net.state_dict().items()}
-        for (t, s), (w, b) in self.masters.items():
+        for (t, s), (w, b) in ((k, v) for k, v in self.masters.items() if k in self.heads):
             for name, p in ((f"posenet.outs.{t}.{s}.conv.weight", w), (f"posenet.outs.{t}.{s}.conv.bias", b)):
                 if name not in sd:
                     raise PosePafError(f"the network has no {name}")
                 sd[name] = p.detach().clone()
+        # a trained convolution: the folded master as the plain weight behind a BN whose fold is the identity in float32, so a model
+        # rebuilt from this dictionary rounds the master's own bits (dividing by the old BN scale would round twice)
+        for (_, t, s), (w, b) in ((k, v) for k, v in self.masters.items() if k in self.convs):
+            base = f"posenet.features.{t}.before_regress.{s}.2."
+            bn = self.net.posenet.features[t].before_regress[s][2].bn
+            new = {"conv.weight": w.detach().permute(0, 3, 1, 2).contiguous()}
+            if bn is None:
+                new["conv.bias"] = b.detach().clone()
+            else:
+                new.update({"bn.weight": torch.ones_like(b), "bn.bias": b.detach().clone(), "bn.running_mean": torch.zeros_like(b),
+                            "bn.running_var": torch.full_like(b, identity_bn_var(bn.eps))})
+            for name, v in new.items():
+                if base + name not in sd:
+                    raise PosePafError(f"the network has no {base + name}")
+                sd[base + name] = v.to(sd[base + name].dtype)
         return sd

@@ -793,6 +793,49 @@ PP_API long long pp_head_wgrad_multi_workspace_bytes(int n_heads, const pp_head_
 PP_API int pp_head_wgrad_multi_f16(int n_heads, const pp_head_wgrad_desc *heads, float inv_loss_scale, const float *inv_loss_scale_dev,
                                    void *workspace, long long workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------- one layer below a head (csrc/posepaf_convgrad.hip)
+ * pp_head_dgrad_f16: the gradient through a 1 x 1 head and the LeakyReLU in front of it.
+ *   s[m][c] = the float32 accumulation, k = 0, 1, ... c_out - 1 in this order, of the EXACT products g[m][k] * w[k][c];
+ *   t = s where y[m][c] > 0, else fl32(slope * s);   dx[m][c] = half_rn(t)   (above 65504: an infinity, which the step's finite test
+ *   then meets in the gradients formed from dx)
+ *   g      DEVICE binary16 (m, ldg), pp_head_wgrad_f16's operand: channels at or behind c_out are never loaded; any 2-byte boundary
+ *          and any ldg >= c_out
+ *   w      DEVICE binary16 (c_out, c_in), the head's weight;  y  DEVICE binary16 (m, c_in) packed, the head's input, that is the
+ *          OUTPUT of the LeakyReLU: slope > 0 keeps the sign of the pre-activation, y = +-0 takes the slope as torch's backward does
+ *   dx     DEVICE binary16 (m, c_in) packed: every element is stored on every call, nothing else is
+ * |dx - exact| <= E + max(2^-11 (|t| + E), 2^-25),  E = a 2^-24 (c_out sum_k |g w| + |s|),  a = 1 or slope: c_out float32 additions,
+ * one float32 multiply, one binary16 rounding.  One launch, no workspace, no atomics; asynchronous, allocates nothing, needs no
+ * pp_ctx, capturable.  Refusals (nothing launched, dx untouched), in this order:  PP_ERR_BAD_ARG: a null g, w, y or dx; m <= 0;
+ * ldg < c_out; g off a 2-byte boundary, w, y or dx off a 16-byte one; slope not finite and positive.  PP_ERR_UNSUPPORTED:
+ * pp_head_dgrad_supported is 0.  PP_ERR_TOO_LARGE: m > 2^31 - 1.  PP_ERR_NO_DEVICE after those. */
+PP_API int pp_head_dgrad_supported(int c_in, int c_out);   /* c_in % 64 == 0, 64..256; c_out 1..64 */
+PP_API int pp_head_dgrad_f16(const void *g, int ldg, const void *w, const void *y, long m, int c_in, int c_out, float slope, void *dx,
+                             void *stream);
+
+/* pp_conv3x3_wgrad_f16: the weight and bias gradient of a 3 x 3 / pad 1 / stride 1 convolution.
+ *   dw[k][r][s][c] = fl32(inv * A),  A the float32 accumulation of the EXACT products dy[b, i, j, k] * x[b, i + r - 1, j + s - 1, c] over
+ *   all pixels whose neighbour lies inside image b (a neighbour outside is not loaded: nothing next to the tensor is ever read);
+ *   db[k] = fl32(inv * sum dy[.][k]);   inv = *inv_loss_scale_dev when that is non-NULL (read when the launch runs), else inv_loss_scale
+ *   dy     DEVICE binary16 (n h w, c_out) packed;  x  DEVICE binary16 NHWC (n, h, w, c_in) packed, the convolution's input
+ *   dw     DEVICE float32 (c_out, 3, 3, c_in): the memory order of a channels-last (c_out, c_in, 3, 3) weight;  db  DEVICE float32
+ *          (c_out): every element is stored on every call, nothing else is
+ * Two plain launches: 9 c_out / 64 sub-problems (tap, 64 output channels) of min(pp_conv3x3_wgrad_max_workgroups(), ceil(n h w / 64))
+ * workgroups each run the head gradient's pass with 64 x c_in + 64 partials per workgroup in the workspace (never assumed zero, no
+ * memset), then a reduction in a fixed order multiplies by inv once.  No floating-point atomics: (n, h, w, c_in, c_out) fixes the
+ * order of the additions, so the bits are equal from run to run, eager or replayed.  A non-finite dy[.][k] makes row k of dw and
+ * db[k] non-finite and leaves every other row its bits.  Asynchronous, allocates nothing, needs no pp_ctx, capturable.
+ * Refusals (nothing launched, outputs untouched), in this order:  PP_ERR_BAD_ARG: a null dy, x, dw, db or workspace; n, h or w <= 0;
+ * dy or x off a 16-byte boundary, dw, db, the workspace or inv_loss_scale_dev off a 4-byte one; with a NULL inv_loss_scale_dev an
+ * inv_loss_scale that is not finite and positive.  PP_ERR_UNSUPPORTED: pp_conv3x3_wgrad_supported is 0.  PP_ERR_TOO_LARGE:
+ * n h w > 2^31 - 1.  PP_ERR_BAD_ARG: a workspace smaller than pp_conv3x3_wgrad_workspace_bytes.  PP_ERR_NO_DEVICE after those. */
+PP_API int pp_conv3x3_wgrad_supported(int c_in, int c_out);   /* c_in % 64 == 0, 64..256; c_out % 64 == 0, 64..256 */
+PP_API int pp_conv3x3_wgrad_max_workgroups(void);             /* per sub-problem */
+/* bytes, or a negative pp_status for arguments pp_conv3x3_wgrad_f16 refuses */
+PP_API long long pp_conv3x3_wgrad_workspace_bytes(int n, int h, int w, int c_in, int c_out);
+PP_API int pp_conv3x3_wgrad_f16(const void *dy, const void *x, int n, int h, int w, int c_in, int c_out, float inv_loss_scale,
+                                const float *inv_loss_scale_dev, void *workspace, long long workspace_bytes, float *dw, float *db,
+                                void *stream);
+
 /* ---------------------------------------------------------------- the heads' optimiser step on the device (csrc/posepaf_headopt.hip)
  * One chain of two launches: the finite test of all n gradients, then -- when every one is finite -- torch.optim.SGD's update
  * (dampening 0, no Nesterov) of the float32 masters, their binary16 copies, and the loss-scale state machine.
@@ -802,7 +845,8 @@ PP_API int pp_head_wgrad_multi_f16(int n_heads, const pp_head_wgrad_desc *heads,
  *   table      DEVICE pp_head_update_desc[n_heads]: where a head's weight and bias lie in the flat tensors and the four binary16
  *              destinations of their nearest-even roundings: weight and wpad receive w_len elements from w_off, bias and bpad b_len
  *              from b_off (the first rows of the zero-padded copies; the rows behind are never touched).  Ranges in ascending
- *              order, disjoint, inside [0, n); an element of no range is updated and copied nowhere
+ *              order, disjoint, inside [0, n); an element of no range is updated and copied nowhere.  A layer without padded copies
+ *              (a 3 x 3 convolution) names its weight as wpad and its bias as bpad too: the second store repeats the first
  *   hyper      DEVICE float[3] = lr, momentum, weight_decay (read when the launch runs: a schedule needs no new capture)
  *   state      DEVICE pp_head_update_state.  A non-finite gradient: masters, momentum and every binary16 copy keep their bits,
  *              skipped += 1, scale = max(scale / 2, min_scale), good_steps = 0.  A finite step: good_steps += 1, and when it reaches
