@@ -19,11 +19,25 @@
 //   k_conv3x3_wgrad_finish adds an element's partials as the head's finish does (four interleaved runs in workgroup order, then
 //   ((s0 + s1) + s2) + s3), multiplies by the factor once and stores dw in (c_out, 3, 3, c_in) order; db comes from the centre tap's
 //   sub-problems.  No atomics, nothing assumed zero: (n, h, w, c_in, c_out) fixes the order of every addition.
+//
+// k_conv3x3_dgrad: dx[b, i, j, c] = half_rn(t),  t = s where y > 0 (or y == NULL) else fl32(slope * s),
+//   s = sum over (r, q, k) with (i + 1 - r, j + 1 - q) inside image b of dy[b, i + 1 - r, j + 1 - q, k] * w[k][r][q][c].
+//   An implicit GEMM on the matrix unit: c_in x 64 pixels per workgroup (an 8 x 8 tile of one image), reduction 9 c_out, all of it in
+//   this workgroup.  The dy halo tile (10 x 10 pixels, zeros -- staged without a load -- where outside the image) goes to LDS ONCE
+//   for all nine taps, already split into bfloat16 hi and lo images (split_bf16: hi + lo is the binary16 value exactly), so the
+//   pixel operand of every MFMA is one 16-byte LDS read.  The weights stream per (tap, 32 output channels) through registers into a
+//   double-buffered LDS image of 32 rows of w -- rows of a fixed tap are contiguous in c, the read is the transposed one of
+//   posepaf_headgrad.h -- and are split once per read (each weight element is read by two waves, one per half of the pixels).  Four
+//   mfma_f32_32x32x16_bf16 per operand pair (hi hi, hi lo, lo hi, lo lo) make every product exact.  A wave owns 32 pixels and
+//   c_in / 64 tiles of 32 channels; the loop runs tap 0 .. 8, k 0 .. c_out - 1 in this order.  The epilogue reads y and stores dx as
+//   8-byte groups of four channels.  No atomics, no workspace: (n, h, w, c_in, c_out) fixes the order of every addition.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
+
+#include <atomic>
 
 #include "posepaf_headgrad.h"
 #include "posepaf_internal.h"
@@ -149,6 +163,163 @@ __global__ __launch_bounds__(HG_THREADS) void k_conv3x3_wgrad_finish(const float
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the 3 x 3 data gradient
+
+constexpr int CD_THREADS = 256;
+constexpr int CD_T = 8;                           // the tile is CD_T x CD_T pixels
+constexpr int CD_HALO = CD_T + 2;
+constexpr int CD_HP = CD_HALO * CD_HALO;          // pixels of the dy halo tile
+constexpr int CD_KS = 32;                         // output channels (rows of w) of a weight slice
+constexpr int CD_PADK = 8;                        // bfloat16 elements of padding behind a halo pixel's row (16 bytes)
+
+constexpr int conv_dgrad_lds_bytes(int c_in, int c_out) {
+    return 2 * CD_HP * (c_out + CD_PADK) * 2 + 2 * CD_KS * (c_in + HG_PAD) * 2;
+}
+
+template <int C_IN>
+__global__ __launch_bounds__(CD_THREADS) void k_conv3x3_dgrad(const __half *__restrict__ dy, const __half *__restrict__ w,
+                                                               const __half *__restrict__ y, int h, int wd, int c_out, int tiles_x, int tiles_y,
+                                                               float slope, __half *__restrict__ dx) {
+    constexpr int WROW = C_IN + HG_PAD;
+    constexpr int VPR = C_IN / 8;                     // 16-byte groups of a row of w
+    constexpr int NV = CD_KS * VPR / CD_THREADS;      // groups of a thread and slice
+    constexpr int NB = C_IN / 64;                     // 32-channel tiles of a wave
+
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int SD = c_out + CD_PADK;
+    unsigned short *s_hi = reinterpret_cast<unsigned short *>(smem), *s_lo = s_hi + CD_HP * SD;
+    __half *s_w = reinterpret_cast<__half *>(s_lo + CD_HP * SD);      // [2][CD_KS * WROW]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned bid = blockIdx.x, tq = bid / (unsigned)tiles_x;
+    const int j0 = CD_T * (int)(bid - tq * (unsigned)tiles_x), i0 = CD_T * (int)(tq % (unsigned)tiles_y);
+    const size_t img_row0 = (size_t)(tq / (unsigned)tiles_y) * (size_t)h;        // the first row of this image, counted over the batch
+
+    // a thread's NV 16-byte groups of the next slice, held in named registers across the MFMA block (an indexed array of them is
+    // not promoted to registers here and lands in scratch)
+    uint4 wr0 = {}, wr1 = {}, wr2 = {}, wr3 = {};
+    static_assert(NV >= 1 && NV <= 4, "wr0 .. wr3");
+    auto load_slice = [&](int it) __attribute__((always_inline)) {
+        const int slices = c_out / CD_KS, tap = it / slices, k0 = CD_KS * (it - tap * slices);
+        auto src = [&](int i) {
+            const int v = tid + CD_THREADS * i, row = v / VPR, cv = v - row * VPR;
+            return reinterpret_cast<const uint4 *>(w + ((size_t)(k0 + row) * 9 + tap) * C_IN + cv * 8);
+        };
+        wr0 = *src(0);
+        if constexpr (NV > 1) wr1 = *src(1);
+        if constexpr (NV > 2) wr2 = *src(2);
+        if constexpr (NV > 3) wr3 = *src(3);
+    };
+    auto stage_slice = [&](int buf) __attribute__((always_inline)) {
+        auto dst = [&](int i) {
+            const int v = tid + CD_THREADS * i, row = v / VPR, cv = v - row * VPR;
+            return reinterpret_cast<uint4 *>(s_w + buf * (CD_KS * WROW) + row * WROW + cv * 8);
+        };
+        *dst(0) = wr0;
+        if constexpr (NV > 1) *dst(1) = wr1;
+        if constexpr (NV > 2) *dst(2) = wr2;
+        if constexpr (NV > 3) *dst(3) = wr3;
+    };
+
+    load_slice(0);
+    // the dy halo tile, once: a pixel outside the image is zeros and is not loaded
+    const int vpp = c_out / 8;
+    for (int v = tid; v < CD_HP * vpp; v += CD_THREADS) {
+        const int pix = v / vpp, cv = v - pix * vpp, hi_ = pix / CD_HALO;
+        const int ii = i0 + hi_ - 1, jj = j0 + (pix - hi_ * CD_HALO) - 1;
+        half8v val = {0, 0, 0, 0, 0, 0, 0, 0};
+        if ((unsigned)ii < (unsigned)h && (unsigned)jj < (unsigned)wd)
+            val = *reinterpret_cast<const half8v *>(dy + ((img_row0 + ii) * (size_t)wd + jj) * c_out + cv * 8);
+        bf8v vh, vl;
+        split_bf16(val, vh, vl);
+        *reinterpret_cast<bf8v *>(s_hi + pix * SD + cv * 8) = vh;
+        *reinterpret_cast<bf8v *>(s_lo + pix * SD + cv * 8) = vl;
+    }
+    stage_slice(0);
+    __syncthreads();
+
+    float16v acc[NB];
+#pragma unroll
+    for (int j = 0; j < NB; j++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[j][r] = 0.0f;
+
+    const int ptile = wave & 1, mt0 = wave >> 1;
+    const int pl = 32 * ptile + (lane & 31), pi = pl >> 3, pj = pl & 7;      // this lane's pixel of the tile
+    const int n_it = 9 * (c_out / CD_KS);
+    for (int it = 0; it < n_it; it++) {
+        const int slices = c_out / CD_KS, tap = it / slices, k0 = CD_KS * (it - tap * slices);
+        const int r = tap / 3, q = tap - 3 * r;
+        if (it + 1 < n_it) load_slice(it + 1);
+        const __half *wimg = s_w + (it & 1) * (CD_KS * WROW);
+        const int drow = ((pi + 2 - r) * CD_HALO + (pj + 2 - q)) * SD + k0 + 8 * (lane >> 5);
+#pragma unroll
+        for (int kk = 0; kk < CD_KS / 16; kk++) {
+            const bf8v b_hi = *reinterpret_cast<const bf8v *>(s_hi + drow + 16 * kk);
+            const bf8v b_lo = *reinterpret_cast<const bf8v *>(s_lo + drow + 16 * kk);
+#pragma unroll
+            for (int j = 0; j < NB; j++) {
+                bf8v a_hi, a_lo;
+                split_bf16(tr_frag(wimg, WROW, 16 * kk, 32 * (mt0 + 2 * j), lane), a_hi, a_lo);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_hi, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_lo, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_hi, acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_lo, acc[j], 0, 0, 0);
+            }
+        }
+        if (it + 1 < n_it) stage_slice((it + 1) & 1);     // the buffer iteration it - 1 read: every wave passed the barrier behind it
+        __syncthreads();
+    }
+
+    // acc[j][reg]: pixel pl, channel 32 (mt0 + 2 j) + (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const int gi = i0 + pi, gj = j0 + pj;
+    if (gi < h && gj < wd) {
+        const size_t base = ((img_row0 + gi) * (size_t)wd + gj) * C_IN;
+#pragma unroll
+        for (int j = 0; j < NB; j++) {
+#pragma unroll
+            for (int rg = 0; rg < 4; rg++) {
+                const int c0 = 32 * (mt0 + 2 * j) + 8 * rg + 4 * (lane >> 5);
+                uint2 yv = make_uint2(0x3c003c00u, 0x3c003c00u);      // y == NULL: every element passes
+                if (y) yv = *reinterpret_cast<const uint2 *>(y + base + c0);
+                // y > 0 as a test of the binary16 bits: sign clear, not zero, not a NaN (a NaN fails y > 0 and takes the slope)
+                auto one = [&](float s, unsigned yb) {
+                    const bool pass = yb - 1u < 0x7c00u;
+                    return (unsigned)__half_as_ushort(__float2half_rn(pass ? s : __fmul_rn(slope, s)));
+                };
+                const unsigned o0 = one(acc[j][4 * rg + 0], yv.x & 0xffffu), o1 = one(acc[j][4 * rg + 1], yv.x >> 16);
+                const unsigned o2 = one(acc[j][4 * rg + 2], yv.y & 0xffffu), o3 = one(acc[j][4 * rg + 3], yv.y >> 16);
+                *reinterpret_cast<uint2 *>(dx + base + c0) = make_uint2(o0 | (o1 << 16), o2 | (o3 << 16));
+            }
+        }
+    }
+}
+
+// The kernel's LDS exceeds the 64 KiB default, so its limit is raised once per DEVICE and instance (a process may hold several
+// GPUs; the flags are atomic, and two threads that both find one clear set the same value twice).  Never inside a stream capture:
+// a first call there is refused with PP_ERR_UNSUPPORTED, as posepaf_conv_own.hip's ensure_attr does -- call once eagerly first.
+constexpr int CD_MAX_DEVICES = 32;
+
+template <int C_IN>
+int launch_conv_dgrad(unsigned blocks, hipStream_t st, const __half *dy, const __half *w, const __half *y, int h, int wd, int c_out,
+                      int tiles_x, int tiles_y, float slope, __half *dx) {
+    static std::atomic<bool> attr_set[CD_MAX_DEVICES];        // zero-initialised
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CD_MAX_DEVICES) return PP_ERR_HIP;
+    if (!attr_set[dev].load(std::memory_order_acquire)) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) return PP_ERR_HIP;
+        if (cs != hipStreamCaptureStatusNone) return PP_ERR_UNSUPPORTED;
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3x3_dgrad<C_IN>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                conv_dgrad_lds_bytes(C_IN, 256)) != hipSuccess)
+            return PP_ERR_HIP;
+        attr_set[dev].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL((k_conv3x3_dgrad<C_IN>), dim3(blocks), dim3(CD_THREADS), conv_dgrad_lds_bytes(C_IN, c_out), st, dy, w, y, h, wd, c_out,
+                       tiles_x, tiles_y, slope, dx);
+    return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
+}
+
 template <int C_IN>
 void launch_dgrad(int grid, hipStream_t st, const __half *g, int ldg, const __half *w, const __half *y, long long m, int c_out, float slope,
                   int n_chunks, __half *dx) {
@@ -238,4 +409,32 @@ extern "C" int pp_conv3x3_wgrad_f16(const void *dy, const void *x, int n, int h,
     hipLaunchKernelGGL(k_conv3x3_wgrad_finish, dim3(c_out * 9 * (c_in / 64) + c_out / 64), dim3(HG_THREADS), 0, st,
                        static_cast<const float *>(partial), grid, c_in, c_out, inv_loss_scale, inv_loss_scale_dev, dw, db);
     return hipGetLastError() == hipSuccess ? PP_OK : PP_ERR_HIP;
+}
+
+extern "C" int pp_conv3x3_dgrad_supported(int c_in, int c_out) { return pp_conv3x3_wgrad_supported(c_in, c_out); }
+
+extern "C" int pp_conv3x3_dgrad_f16(const void *dy, const void *w, const void *y, int n, int h, int wd, int c_in, int c_out, float slope,
+                                    void *dx, void *stream) {
+    if (!dy || !w || !dx) return PP_ERR_BAD_ARG;
+    if (n <= 0 || h <= 0 || wd <= 0) return PP_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(dy) % 16 || reinterpret_cast<uintptr_t>(w) % 16 || reinterpret_cast<uintptr_t>(y) % 16 ||
+        reinterpret_cast<uintptr_t>(dx) % 16)
+        return PP_ERR_BAD_ARG;
+    if (y && !(isfinite(slope) && slope > 0.0f)) return PP_ERR_BAD_ARG;
+    if (!pp_conv3x3_dgrad_supported(c_in, c_out)) return PP_ERR_UNSUPPORTED;
+    const long long rows = (long long)n * h;        // < 2^62
+    if (rows > 2147483647ll || rows * wd > 2147483647ll) return PP_ERR_TOO_LARGE;
+    if (!device_present()) return PP_ERR_NO_DEVICE;
+
+    const int tiles_x = (wd + CD_T - 1) / CD_T, tiles_y = (h + CD_T - 1) / CD_T;
+    const unsigned blocks = (unsigned)((long long)n * tiles_y * tiles_x);      // <= n h w
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const __half *dyh = static_cast<const __half *>(dy), *wh = static_cast<const __half *>(w), *yh = static_cast<const __half *>(y);
+    __half *dh = static_cast<__half *>(dx);
+    switch (c_in) {
+        case 64: return launch_conv_dgrad<64>(blocks, st, dyh, wh, yh, h, wd, c_out, tiles_x, tiles_y, slope, dh);
+        case 128: return launch_conv_dgrad<128>(blocks, st, dyh, wh, yh, h, wd, c_out, tiles_x, tiles_y, slope, dh);
+        case 192: return launch_conv_dgrad<192>(blocks, st, dyh, wh, yh, h, wd, c_out, tiles_x, tiles_y, slope, dh);
+        default: return launch_conv_dgrad<256>(blocks, st, dyh, wh, yh, h, wd, c_out, tiles_x, tiles_y, slope, dh);
+    }
 }

@@ -56,6 +56,8 @@ evaluate.py -p loads); val_loss.focal_l2_terms -> combine -> backward() (pp_foca
   --train heads+conv (with --model fused --arch final | auto) the 3 x 3 convolution in front of every head is trained as well:
                   pp_head_dgrad_f16 and pp_conv3x3_wgrad_f16 per layer, float32 masters of the folded weight and bias in the same
                   flat tensors, update, scale and capture as the heads
+  --train heads+conv2 (the same preconditions) the 3 x 3 convolution in front of that one as well: pp_conv3x3_dgrad_f16 takes the
+                  gradient through the upper convolution, --update device goes through pp_layer_update_f32
 
 Prints one JSON line: losses (per step), loss_first, loss_last, grad_norm_first (L2 norm of the updated parameters' gradients at
 step 0), seconds, steps_per_s (steady state: from the second step on, with --graph from the third, so without the first step's set-up
@@ -87,8 +89,9 @@ def parse(argv=None):
     ap.add_argument("--sizes", default="128x128", help="image size HxW: one size, both sides multiples of 64")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--stages", type=int, default=4, help="hourglass stages of the network (a checkpoint must hold as many)")
-    ap.add_argument("--train", choices=("all", "heads", "heads+conv"), default="all",
-                    help="heads+conv (with --model fused --arch final | auto): the 3 x 3 convolution in front of every head as well")
+    ap.add_argument("--train", choices=("all", "heads", "heads+conv", "heads+conv2"), default="all",
+                    help="heads+conv (with --model fused --arch final | auto): the 3 x 3 convolution in front of every head as well; "
+                         "heads+conv2: both 3 x 3 convolutions below every head")
     ap.add_argument("--lr", type=float, default=2.5e-5)
     ap.add_argument("--loss", choices=("device", "torch"), default="device")
     ap.add_argument("-p", "--checkpoint_path", default=None)
@@ -155,11 +158,11 @@ def refusals(a):
         out.append("--batch and --steps must be at least 1")
     if a.model == "fused":
         from posepaf.head_train import is_power_of_two
-        if a.train not in ("heads", "heads+conv"):
+        if a.train not in ("heads", "heads+conv", "heads+conv2"):
             out.append("--model fused trains the heads, or with --train heads+conv the convolution in front of each as well (the fused "
-                       "model has no other backward): pass --train heads or --train heads+conv")
-        if a.train == "heads+conv" and a.arch not in ("final", "auto"):
-            out.append("--train heads+conv needs --arch final (or auto): on posenet an SE block stands between the convolution and the head")
+                       "model has no other backward): pass --train heads or --train heads+conv (heads+conv2: both convolutions)")
+        if a.train in ("heads+conv", "heads+conv2") and a.arch not in ("final", "auto"):
+            out.append(f"--train {a.train} needs --arch final (or auto): on posenet an SE block stands between the convolution and the head")
         if a.loss != "device":
             out.append("--model fused takes the loss gradient from pp_focal_l2_grad: --loss torch belongs to --model plain")
         if a.loss_scale not in ("auto", "dynamic") and not is_power_of_two(a.loss_scale):
@@ -173,8 +176,8 @@ def refusals(a):
             out.append("--growth_interval must be at least 0")
         elif a.growth_given and a.loss_scale != "dynamic":
             out.append("--growth_interval belongs to --loss_scale dynamic")
-    elif a.train == "heads+conv":
-        out.append("--train heads+conv belongs to --model fused (--arch final | auto)")
+    elif a.train in ("heads+conv", "heads+conv2"):
+        out.append(f"--train {a.train} belongs to --model fused (--arch final | auto)")
     elif a.arch != "posenet" or a.loss_scale != "auto" or a.wgrad != "device" or a.graph or a.update_given or a.growth_given:
         out.append("--arch, --loss_scale, --wgrad, --update, --graph and --growth_interval belong to --model fused")
     sizes = a.sizes.split(",")

@@ -50,7 +50,8 @@ EXPORTS = [
     "pp_head_wgrad_f16", "pp_head_wgrad_multi_max_heads", "pp_head_wgrad_multi_workspace_bytes", "pp_head_wgrad_multi_f16",
     "pp_head_update_workspace_bytes", "pp_head_update_f32",
     "pp_head_dgrad_supported", "pp_head_dgrad_f16", "pp_conv3x3_wgrad_supported", "pp_conv3x3_wgrad_max_workgroups",
-    "pp_conv3x3_wgrad_workspace_bytes", "pp_conv3x3_wgrad_f16",
+    "pp_conv3x3_wgrad_workspace_bytes", "pp_conv3x3_wgrad_f16", "pp_conv3x3_dgrad_supported", "pp_conv3x3_dgrad_f16",
+    "pp_layer_update_max_segments", "pp_layer_update_f32",
     # the reference's seven names (utils/pafprocess/pafprocess.h:70-76)
     "process_paf", "get_num_humans", "get_part_peak_id", "get_score", "get_part_x", "get_part_y", "get_part_score",
 ]
@@ -91,6 +92,11 @@ class HeadUpdateDesc(C.Structure):
     """pp_head_update_desc (include/posepaf.h)"""
     _fields_ = [("w_off", C.c_longlong), ("w_len", C.c_longlong), ("b_off", C.c_longlong), ("b_len", C.c_longlong),
                 ("weight", C.c_void_p), ("bias", C.c_void_p), ("wpad", C.c_void_p), ("bpad", C.c_void_p)]
+
+
+class UpdateSegment(C.Structure):
+    """pp_update_segment (include/posepaf.h)"""
+    _fields_ = [("off", C.c_longlong), ("len", C.c_longlong), ("dst", C.c_void_p), ("dst2", C.c_void_p)]
 
 
 # pp_head_update_state (include/posepaf.h)
@@ -180,6 +186,10 @@ def load():
     L.pp_conv3x3_wgrad_workspace_bytes.argtypes = [C.c_int] * 5
     L.pp_conv3x3_wgrad_workspace_bytes.restype = C.c_longlong
     L.pp_conv3x3_wgrad_f16.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_longlong, vp, vp, vp]
+    L.pp_conv3x3_dgrad_supported.argtypes = [C.c_int, C.c_int]
+    L.pp_conv3x3_dgrad_f16.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
+    L.pp_layer_update_max_segments.argtypes = []
+    L.pp_layer_update_f32.argtypes = [vp, vp, vp, C.c_long, vp, C.c_int, vp, vp, vp, vp]
     L.pp_flip_average.argtypes =[vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.pp_pwconv_supported.argtypes = [C.c_int, C.c_int]
     L.pp_pwconv_f16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_float, C.c_int, vp]

@@ -48,6 +48,16 @@ pp_conv3x3_wgrad_f16 forms dw / db from dY and the convolution's captured input 
 forms both in float64 with the contract's roundings.  The same flat tensors, finite test, update paths, dynamic scale and capture
 cover them.  gradients() returns them under ("conv", t, s); state_dict() writes the folded master as the plain convolution's weight
 behind a BN whose fold is exact (identity_bn_var), so a model rebuilt from it runs the trainer's binary16 bits.
+
+train="heads+conv2" ('final' only).  The 3 x 3 convolution in front of that one (before_regress[s][1], the
+fused model's feat[t][s].c2) is trained as well.  Its masters lie BEHIND the heads' and the ("conv", t, s) ones in the flat tensors,
+so the ranges of those keys are the ones of "heads+conv".  Per (t, s), after c3's gradients: pp_conv3x3_dgrad_f16 takes c3's dY
+through c3's CURRENT binary16 weight -- the layer's own channels-last memory, no rotated copy -- and the LeakyReLU whose output is
+c3's captured input (dY2, binary16); pp_conv3x3_wgrad_f16 forms c2's dw / db from dY2 and c2's captured input with the same factor
+and workspace.  wgrad="torch": torch.nn.grad.conv2d_input in float64 with the contract's roundings, then conv2d_weight as for c3.
+update="device" goes through pp_layer_update_f32 in this mode (60 layers at four stages; pp_head_update_f32 takes 40): a head is two
+segments with its padded copy as the second destination, a convolution two with dst2 = dst.  gradients() returns ("conv2", t, s)
+next to the others; last_inputs[("conv2", t, s)] = (c3's binary16 weight (K, 3, 3, C) copy, c2's NHWC input, dY2).
 """
 import ctypes as C
 import math
@@ -149,10 +159,11 @@ class HeadTrainer:
         found = "final" if isinstance(pn, posenet_final.PoseNet) else "posenet"
         if arch not in (None, found):
             raise PosePafError(f"arch = {arch!r}, the network is {found!r}")
-        if train not in ("heads", "heads+conv"):
-            raise PosePafError(f"train = {train!r}: 'heads' or 'heads+conv' (the 3 x 3 convolution in front of every head as well)")
-        if train == "heads+conv" and found != "final":
-            raise PosePafError("train='heads+conv' needs the 'final' architecture: on 'posenet' an SE block stands between the "
+        if train not in ("heads", "heads+conv", "heads+conv2"):
+            raise PosePafError(f"train = {train!r}: 'heads', 'heads+conv' (the 3 x 3 convolution in front of every head as well) or "
+                               "'heads+conv2' (both 3 x 3 convolutions below every head)")
+        if train != "heads" and found != "final":
+            raise PosePafError(f"train={train!r} needs the 'final' architecture: on 'posenet' an SE block stands between the "
                                "convolution and the head, and it has no backward here")
         for t, stage in enumerate(pn.outs):
             for s, c in enumerate(stage):
@@ -174,10 +185,14 @@ class HeadTrainer:
         for key in self.heads:
             conv = pn.outs[key[0]][key[1]].conv
             sources[key] = (conv.weight.detach(), conv.bias.detach())
-        if train == "heads+conv":       # behind the heads, so that their ranges are those of train='heads'
+        if train != "heads":            # behind the heads, so that their ranges are those of train='heads'
             for t, s in self.heads:
                 sources[("conv", t, s)] = self._conv_source(pn, t, s)
                 self.convs[("conv", t, s)] = self.model.feat[t][s].c3
+        if train == "heads+conv2":      # and behind those: the ranges of the keys above are the ones of train='heads+conv'
+            for t, s in self.heads:
+                sources[("conv2", t, s)] = self._conv_source(pn, t, s, 1)
+                self.convs[("conv2", t, s)] = self.model.feat[t][s].c2
         sizes = {key: (w.numel(), b.numel()) for key, (w, b) in sources.items()}
         total = sum(a + b for a, b in sizes.values())
         self._flat = torch.empty(total, dtype=torch.float32, device=device)
@@ -209,21 +224,25 @@ class HeadTrainer:
             layer.register_forward_pre_hook(lambda mod, args, key=key: self._seen.__setitem__(key, args[0]))
         self._push_masters()
 
-    def _conv_source(self, pn, t, s):
-        """(weight (K, 3, 3, C), bias (K,)) float32 of before_regress[s][2] of stage t with its BN folded in float32 (fused_model._fold on
-        the plain layer, not the fused model's binary16 copy), the weight in the memory order of the fused layer's channels-last tensor"""
+    def _conv_source(self, pn, t, s, layer=2):
+        """(weight (K, 3, 3, C), bias (K,)) float32 of before_regress[s][layer] of stage t (2: the convolution in front of the head, 1:
+        the one in front of that) with its BN folded in float32 (fused_model._fold on the plain layer, not the fused model's binary16
+        copy), the weight in the memory order of the fused layer's channels-last tensor"""
         import torch
         from . import _lib, fused_model
-        blk = pn.features[t].before_regress[s][2]
-        c3, conv = self.model.feat[t][s].c3, blk.conv
+        blk = pn.features[t].before_regress[s][layer]
+        fused, conv = getattr(self.model.feat[t][s], f"c{layer + 1}"), blk.conv
         plain = (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups)
-        if plain != ((3, 3), (1, 1), (1, 1), (1, 1), 1) or blk.relu is None or not c3.act:
-            raise PosePafError(f"before_regress[{s}][2] of stage {t} is not a 3 x 3 / pad 1 / stride 1 convolution with a LeakyReLU")
+        if plain != ((3, 3), (1, 1), (1, 1), (1, 1), 1) or blk.relu is None or not fused.act:
+            raise PosePafError(f"before_regress[{s}][{layer}] of stage {t} is not a 3 x 3 / pad 1 / stride 1 convolution with a LeakyReLU")
         k, c = conv.weight.shape[:2]
         L = _lib.load()
-        if not L.pp_conv3x3_wgrad_supported(c, k) or not L.pp_head_dgrad_supported(k, self.heads[(t, s)].k_real):
-            raise PosePafError(f"before_regress[{s}][2] of stage {t}: {c} -> {k} channels are outside the gradient kernels' shapes")
-        if c3.weight.dtype != torch.float16 or not c3.weight.is_contiguous(memory_format=torch.channels_last):
+        # what takes the gradient to this layer's output: the head's data gradient, or the data gradient of the 3 x 3 above
+        reach = L.pp_head_dgrad_supported(k, self.heads[(t, s)].k_real) if layer == 2 else L.pp_conv3x3_dgrad_supported(
+            k, self.model.feat[t][s].c3.weight.shape[0])
+        if not L.pp_conv3x3_wgrad_supported(c, k) or not reach:
+            raise PosePafError(f"before_regress[{s}][{layer}] of stage {t}: {c} -> {k} channels are outside the gradient kernels' shapes")
+        if fused.weight.dtype != torch.float16 or not fused.weight.is_contiguous(memory_format=torch.channels_last):
             raise PosePafError("the fused 3 x 3 layer does not keep its weight as one channels-last binary16 tensor")
         w, b = fused_model._fold(conv, blk.bn)
         return w.permute(0, 2, 3, 1).contiguous(), b
@@ -265,7 +284,10 @@ class HeadTrainer:
         import torch
         from . import _lib
         L = _lib.load()
-        if len(sizes) > L.pp_head_wgrad_multi_max_heads():
+        self._segments = self.train == "heads+conv2"      # this mode always updates through pp_layer_update_f32
+        if self._segments and 2 * len(sizes) > L.pp_layer_update_max_segments():
+            raise PosePafError(f"{len(sizes)} trained layers: pp_layer_update_f32 takes {L.pp_layer_update_max_segments()} segments")
+        if not self._segments and len(sizes) > L.pp_head_wgrad_multi_max_heads():
             raise PosePafError(f"{len(sizes)} trained layers: pp_head_update_f32 takes {L.pp_head_wgrad_multi_max_heads()}")
         dev = self.device
         self._hyper = torch.tensor([lr, momentum, weight_decay], dtype=torch.float32, device=dev)
@@ -281,7 +303,8 @@ class HeadTrainer:
             nw, nb = sizes[key]
             self._ranges.append((at, nw, at + nw, nb))
             at += nw + nb
-        self._table = torch.zeros(len(sizes) * C.sizeof(_lib.HeadUpdateDesc), dtype=torch.uint8, device=dev)
+        entry = 2 * C.sizeof(_lib.UpdateSegment) if self._segments else C.sizeof(_lib.HeadUpdateDesc)
+        self._table = torch.zeros(len(sizes) * entry, dtype=torch.uint8, device=dev)
         self._table_ptrs = None
         self._update_ws = torch.empty(int(L.pp_head_update_workspace_bytes(self._flat.numel())), dtype=torch.uint8, device=dev)
 
@@ -310,9 +333,10 @@ class HeadTrainer:
             return
         if torch.cuda.is_current_stream_capturing():
             raise PosePafError("a head's fp16 tensor moved after the eager step: the captured update would write the old one")
-        table = (_lib.HeadUpdateDesc * len(ptrs))()
+        # pp_head_update_f32's descriptors, or the same ranges as single segments (pp_layer_update_f32): the one this mode calls
+        table = (_lib.UpdateSegment * (2 * len(ptrs)))() if self._segments else (_lib.HeadUpdateDesc * len(ptrs))()
         layers = list(self.heads.values()) + list(self.convs.values())
-        for d, layer, (w_off, w_len, b_off, b_len), (pw, pb, pwp, pbp) in zip(table, layers, self._ranges, ptrs):
+        for i, (layer, (w_off, w_len, b_off, b_len), (pw, pb, pwp, pbp)) in enumerate(zip(layers, self._ranges, ptrs)):
             if hasattr(layer, "wpad"):
                 k = layer.k_real
                 for t, n in ((layer.weight, w_len), (layer.bias, b_len), (layer.wpad[:k], w_len), (layer.bpad[:k], b_len)):
@@ -324,7 +348,13 @@ class HeadTrainer:
                 if (w.dtype != torch.float16 or b.dtype != torch.float16 or w.numel() != w_len or b.numel() != b_len
                         or not w.is_contiguous(memory_format=torch.channels_last) or not b.is_contiguous()):
                     raise PosePafError("a convolution's fp16 tensor is not the dense binary16 image of its master")
-            d.w_off, d.w_len, d.b_off, d.b_len, d.weight, d.bias, d.wpad, d.bpad = w_off, w_len, b_off, b_len, pw, pb, pwp, pbp
+            if self._segments:
+                sw, sb = table[2 * i], table[2 * i + 1]
+                sw.off, sw.len, sw.dst, sw.dst2 = w_off, w_len, pw, pwp
+                sb.off, sb.len, sb.dst, sb.dst2 = b_off, b_len, pb, pbp
+            else:
+                d = table[i]
+                d.w_off, d.w_len, d.b_off, d.b_len, d.weight, d.bias, d.wpad, d.bpad = w_off, w_len, b_off, b_len, pw, pb, pwp, pbp
         self._table.copy_(torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()))
         self._table_ptrs = ptrs
 
@@ -333,9 +363,11 @@ class HeadTrainer:
         from . import _lib
         self._sync_table()
         ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(_lib.load().pp_head_update_f32(ptr(self._flat), ptr(self._flat_grad), ptr(self._flat_buf), self._flat.numel(),
-                                                  ptr(self._table), len(self.heads) + len(self.convs), ptr(self._hyper), ptr(self._state), ptr(self._update_ws),
-                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        L, layers = _lib.load(), len(self.heads) + len(self.convs)
+        entry, n = (L.pp_layer_update_f32, 2 * layers) if self._segments else (L.pp_head_update_f32, layers)
+        _lib.check(entry(ptr(self._flat), ptr(self._flat_grad), ptr(self._flat_buf), self._flat.numel(), ptr(self._table), n,
+                         ptr(self._hyper), ptr(self._state), ptr(self._update_ws),
+                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def _check_inputs(self, x, target, mask):
         import torch
@@ -454,7 +486,13 @@ class HeadTrainer:
                     self._wgrad(key, g2, ldg, x2, scale, inv)
             if self.wgrad == "multi":
                 self._wgrad_multi(inv)
-            for key, c3 in self.convs.items():
+            for key, c3 in self.convs.items():      # every ("conv", t, s) before the first ("conv2", t, s)
+                if key[0] == "conv2":
+                    above = self.convs[("conv",) + key[1:]]
+                    self.last_inputs[key] = (above.weight.detach().permute(0, 2, 3, 1).contiguous().clone(),
+                                             self._seen[key].permute(0, 2, 3, 1).contiguous(), None)
+                    self._conv2_grads(key, inv, self.wgrad)
+                    continue
                 head = self.heads[key[1:]]
                 self.last_inputs[key] = (head.weight.detach().reshape(head.k_real, -1).clone(),
                                          self._seen[key].permute(0, 2, 3, 1).contiguous(), None)
@@ -501,6 +539,50 @@ class HeadTrainer:
                                           C.c_void_p(self._workspace.data_ptr()), need, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()),
                                           stream))
         self.last_inputs[key] = (w16, x_in, dy)
+
+    def _conv2_grads(self, key, inv, how):
+        """("conv2", t, s): dY2 = ("conv", t, s)'s dY through that convolution and the LeakyReLU in front of it, then this
+        convolution's dw / db into the masters' .grad, from last_inputs: ("conv", t, s)'s (., NHWC input = the activation's output, dY)
+        and this key's (c3 weight (K, 3, 3, C), NHWC input, .); the third element becomes dY2.  how 'torch': both steps in float64
+        with the contract's roundings; else pp_conv3x3_dgrad_f16 and pp_conv3x3_wgrad_f16.  inv as in _conv_grads"""
+        import torch
+        from . import _lib, fused_model
+        _, y_mid, dy = self.last_inputs[("conv",) + key[1:]]
+        w16, x_in = self.last_inputs[key][:2]
+        dw, db = self._grads[key]
+        B, h, w, c_in = x_in.shape
+        c_top, c_mid = w16.shape[0], w16.shape[3]
+        m = B * h * w
+        if (dy is None or tuple(dy.shape) != (m, c_top) or tuple(y_mid.shape) != (B, h, w, c_mid) or tuple(w16.shape[1:3]) != (3, 3)
+                or tuple(dw.shape) != (c_mid, 3, 3, c_in)):
+            raise PosePafError(f"{key}: the captured input of the convolution above is not this convolution's output")
+        if how == "torch":
+            s = torch.nn.grad.conv2d_input((B, c_mid, h, w), w16.double().permute(0, 3, 1, 2),
+                                           dy.double().view(B, h, w, c_top).permute(0, 3, 1, 2), stride=1, padding=1).permute(0, 2, 3, 1)
+            t = torch.where(y_mid > 0, s, (float(np.float32(fused_model.LEAK)) * s).float().double())       # fl32(slope * s)
+            dy2 = t.half().reshape(m, c_mid)
+            d64 = dy2.double()
+            g64 = torch.nn.grad.conv2d_weight(x_in.double().permute(0, 3, 1, 2), (c_mid, c_in, 3, 3),
+                                              d64.view(B, h, w, c_mid).permute(0, 3, 1, 2), stride=1, padding=1)
+            dw.copy_(g64.permute(0, 2, 3, 1).float() * inv)
+            db.copy_(d64.sum(dim=0).float() * inv)
+            self.last_inputs[key] = (w16, x_in, dy2)
+            return
+        L = _lib.load()
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        dy2 = torch.empty((m, c_mid), dtype=torch.float16, device=self.device)
+        _lib.check(L.pp_conv3x3_dgrad_f16(C.c_void_p(dy.data_ptr()), C.c_void_p(w16.data_ptr()), C.c_void_p(y_mid.data_ptr()), B, h, w, c_mid,
+                                          c_top, fused_model.LEAK, C.c_void_p(dy2.data_ptr()), stream))
+        need = int(L.pp_conv3x3_wgrad_workspace_bytes(B, h, w, c_in, c_mid))
+        if need < 0:
+            _lib.check(need)
+        self._grow_workspace(need)
+        on_device = isinstance(inv, torch.Tensor)
+        _lib.check(L.pp_conv3x3_wgrad_f16(C.c_void_p(dy2.data_ptr()), C.c_void_p(x_in.data_ptr()), B, h, w, c_in, c_mid,
+                                          1.0 if on_device else inv, C.c_void_p(inv.data_ptr()) if on_device else None,
+                                          C.c_void_p(self._workspace.data_ptr()), need, C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()),
+                                          stream))
+        self.last_inputs[key] = (w16, x_in, dy2)
 
     def _push_masters(self):
         """the masters, rounded to binary16, in place into the fused heads' tensors"""
@@ -549,7 +631,7 @@ class HeadTrainer:
                         g2, ldg, x2, scale = self.last_inputs[key]
                         self._wgrad(key, g2, ldg, x2, scale, inv)
                 for key in self.convs:
-                    self._conv_grads(key, inv, wgrad)
+                    (self._conv2_grads if key[0] == "conv2" else self._conv_grads)(key, inv, wgrad)
         finally:
             self.wgrad = keep
         return self._grad_copies()
@@ -623,9 +705,10 @@ class HeadTrainer:
                 sd[name] = p.detach().clone()
         # a trained convolution: the folded master as the plain weight behind a BN whose fold is the identity in float32, so a model
         # rebuilt from this dictionary rounds the master's own bits (dividing by the old BN scale would round twice)
-        for (_, t, s), (w, b) in ((k, v) for k, v in self.masters.items() if k in self.convs):
-            base = f"posenet.features.{t}.before_regress.{s}.2."
-            bn = self.net.posenet.features[t].before_regress[s][2].bn
+        for (kind, t, s), (w, b) in ((k, v) for k, v in self.masters.items() if k in self.convs):
+            layer = 1 if kind == "conv2" else 2
+            base = f"posenet.features.{t}.before_regress.{s}.{layer}."
+            bn = self.net.posenet.features[t].before_regress[s][layer].bn
             new = {"conv.weight": w.detach().permute(0, 3, 1, 2).contiguous()}
             if bn is None:
                 new["conv.bias"] = b.detach().clone()

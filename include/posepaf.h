@@ -836,6 +836,29 @@ PP_API int pp_conv3x3_wgrad_f16(const void *dy, const void *x, int n, int h, int
                                 const float *inv_loss_scale_dev, void *workspace, long long workspace_bytes, float *dw, float *db,
                                 void *stream);
 
+/* pp_conv3x3_dgrad_f16: the data gradient of a 3 x 3 / pad 1 / stride 1 convolution and the LeakyReLU in front of it.
+ *   s[b, i, j, c] = the float32 accumulation of the EXACT products dy[b, i + 1 - r, j + 1 - q, k] * w[k][r][q][c] over the (r, q, k)
+ *   whose dy pixel lies inside image b (a pixel outside is not loaded: nothing next to the tensor and nothing of image b +- 1 is read);
+ *   t = s where y > 0 or y == NULL, else fl32(slope * s) (y = +-0 takes the slope, as in pp_head_dgrad_f16);   dx = half_rn(t)
+ *   (above 65504: an infinity, which the step's finite test then meets)
+ *   dy     DEVICE binary16 (n h w, c_out) packed: what pp_head_dgrad_f16 writes
+ *   w      DEVICE binary16 (c_out, 3, 3, c_in): the memory of a channels-last (c_out, c_in, 3, 3) weight, as it is -- no rotated or
+ *          transposed copy
+ *   y      DEVICE binary16 NHWC (n, h, w, c_in) packed, or NULL: the OUTPUT of the LeakyReLU that produced this convolution's input
+ *   dx     DEVICE binary16 NHWC (n, h, w, c_in) packed: every element is stored on every call, nothing else is
+ * One launch: a workgroup owns an 8 x 8 pixel tile of one image, all c_in channels and the whole reduction of 9 c_out; products on
+ * the matrix unit from operands split into bfloat16 hi + lo (four MFMAs per pair, every product exact, subnormals included), taps
+ * 0 .. 8 and k ascending.  (n, h, w, c_in, c_out) alone fixes the order of the additions: equal bits from call to call, eager or
+ * replayed.  No atomics, no split of the reduction across workgroups, no workspace.  For any order and an accumulate that may
+ * truncate:  |dx - exact| <= E + max(2^-11 (|t| + E), 2^-25),  E = a (9 c_out 2^-23 sum |dy w| + 2^-24 |s|),  a = 1 or slope.
+ * Asynchronous, allocates nothing, needs no pp_ctx, capturable once a call of that c_in has run eagerly on the device: the
+ * first one raises the kernel's LDS limit (once per device) and is refused with PP_ERR_UNSUPPORTED inside a stream capture.  Refusals (nothing launched, dx untouched), in this order:  PP_ERR_BAD_ARG: a null dy, w or
+ * dx; n, h or wd <= 0; dy, w, y or dx off a 16-byte boundary; a non-NULL y with a slope that is not finite and positive.
+ * PP_ERR_UNSUPPORTED: pp_conv3x3_dgrad_supported is 0.  PP_ERR_TOO_LARGE: n h wd > 2^31 - 1.  PP_ERR_NO_DEVICE after those. */
+PP_API int pp_conv3x3_dgrad_supported(int c_in, int c_out);   /* both % 64 == 0, 64..256: pp_conv3x3_wgrad_supported's set */
+PP_API int pp_conv3x3_dgrad_f16(const void *dy, const void *w, const void *y, int n, int h, int wd, int c_in, int c_out, float slope,
+                                void *dx, void *stream);
+
 /* ---------------------------------------------------------------- the heads' optimiser step on the device (csrc/posepaf_headopt.hip)
  * One chain of two launches: the finite test of all n gradients, then -- when every one is finite -- torch.optim.SGD's update
  * (dampening 0, no Nesterov) of the float32 masters, their binary16 copies, and the loss-scale state machine.
@@ -870,6 +893,22 @@ typedef struct {
 PP_API long long pp_head_update_workspace_bytes(long n);
 PP_API int pp_head_update_f32(float *masters, const float *grads, float *momentum, long n, const pp_head_update_desc *table, int n_heads,
                               const float *hyper, pp_head_update_state *state, void *workspace, void *stream);
+
+/* pp_layer_update_f32: pp_head_update_f32 -- the same two launches, finite test over all n, three SGD roundings, loss-scale state
+ * machine and workspace (pp_head_update_workspace_bytes(n)) -- for more layers than 40 heads: the table is a DEVICE array of single
+ * segments, ascending, disjoint, inside [0, n).  Elements off .. off + len - 1 of the masters are rounded to binary16 (nearest
+ * even) into dst and dst2, which may be equal (a layer without a padded copy).  One copy of the device arithmetic serves both
+ * entries.  Refusals before any launch: PP_ERR_BAD_ARG for a null pointer, n <= 0, n_segments < 0, masters / grads / momentum /
+ * hyper / workspace off a 4-byte boundary, segments / state off an 8-byte one; PP_ERR_UNSUPPORTED for n_segments >
+ * PP_LAYER_UPDATE_MAX_SEGMENTS; PP_ERR_TOO_LARGE for n > 2^31 - 1; PP_ERR_NO_DEVICE last. */
+#define PP_LAYER_UPDATE_MAX_SEGMENTS 256     /* 8 stacks x 5 scales x 3 layers x (weight, bias) = 240 */
+typedef struct {
+    long long off, len;
+    void *dst, *dst2;
+} pp_update_segment;
+PP_API int pp_layer_update_max_segments(void);
+PP_API int pp_layer_update_f32(float *masters, const float *grads, float *momentum, long n, const pp_update_segment *segments,
+                               int n_segments, const float *hyper, pp_head_update_state *state, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------- Python twins, host form
  * utils.parse_skeletons.find_connections / find_humans (:324-600) with host arrays, for callers of the non --run_cpp

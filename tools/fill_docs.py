@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Substitute the @PLACEHOLDER@ numbers of DESIGN.md / README.md from the bench lines kept under profiles/ (round 3).
+"""Substitute the @PLACEHOLDER@ numbers of DESIGN.md / README.md from the bench lines kept under profiles/ (round 3) and the
+tables of DESIGN section 6, round 27, from the probes' JSON (numbers only: the prose lives in the templates).
 Idempotent: the templates live in DESIGN.md.in / README.md.in next to the outputs."""
 import json
 import os
 import re
+import statistics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,6 +26,34 @@ vals = {
     "MSFWD": f"{m['roofline_forward']['frac']:.2f}", "CPU": f"{d['cpu_baseline']['value']:.0f}",
     "CPU1": f"{d['cpu_baseline']['single_core']['value']:.1f}",
 }
+
+
+def round27():
+    """the tables of DESIGN section 6, round 27, from profiles/r27_conv_dgrad.json (tools/conv_dgrad_probe.py)"""
+    doc = json.load(open(os.path.join(ROOT, "profiles", "r27_conv_dgrad.json")))
+    span = lambda r, u, f: f"{r['median_' + u]:{f}} ({r['min_' + u]:{f}} – {r['max_' + u]:{f}})"
+    rows = []
+    for side, r in doc["kernel"].items():
+        k, t = r["pp_conv3x3_dgrad_f16"], r["torch conv2d_input, binary16"]
+        rows.append(f"| {side.split('x')[0]}² | {r['m']} | {span(k, 'us', '.1f')} | {k['floor_us_at_8TBs']:.1f} | {k['useful_tflops']:.1f} | {span(t, 'us', '.1f')} |")
+    step = doc["step"]
+    srows = [f"| `train=\"{m}\"` | {step[m]['median_ms_per_step']:.2f} | {step[m]['min_ms_per_step']:.2f} – {step[m]['max_ms_per_step']:.2f} | "
+             f"{step[m]['graph_replays']} | {step[m]['skipped_steps']} |" for m in ("heads", "heads+conv", "heads+conv2")]
+    add = step["heads+conv2"]["median_ms_per_step"] - step["heads+conv"]["median_ms_per_step"]
+    dg = sum(r["pp_conv3x3_dgrad_f16"]["median_us"] for r in doc["kernel"].values()) / 1e3
+    wg = sum(r["pp_conv3x3_wgrad_f16"]["median_us"] for r in
+             json.load(open(os.path.join(ROOT, "profiles", "r26_conv_wgrad.json")))["kernel"].values()) / 1e3
+    cmp = doc["against_the_parent_commit"]
+    prows = [f"| `train=\"{mode}\"` | {span(cmp[mode]['this'], 'ms_per_step', '.2f')} | {span(cmp[mode]['parent'], 'ms_per_step', '.2f')} | "
+             f"{'yes' if cmp[mode]['this_median_inside_the_parents_range'] else 'no'} |" for mode in ("heads", "heads+conv")]
+    procs = [f"| {i} | {r['version']} | " + " | ".join(f"{statistics.median(r['ms_per_step'][m]):.2f} ({min(r['ms_per_step'][m]):.2f} – "
+                                                        f"{max(r['ms_per_step'][m]):.2f})" for m in ("heads", "heads+conv"))
+             + f" | {r['kernel_choices']['hash']} ({r['kernel_choices']['entries']}) |" for i, r in enumerate(cmp["processes"])]
+    return {"R27KERNEL": "\n".join(rows), "R27STEP": "\n".join(srows), "R27ADD": f"{add:.2f}", "R27DG": f"{dg:.2f}", "R27WG": f"{wg:.2f}",
+            "R27ACC": f"{4 * (dg + wg):.1f}", "R27PARENT": "\n".join(prows), "R27PROCESSES": "\n".join(procs)}
+
+
+vals.update(round27())
 for name in ("DESIGN.md", "README.md"):
     src = os.path.join(ROOT, name + ".in")
     if not os.path.exists(src):
