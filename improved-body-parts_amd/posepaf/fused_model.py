@@ -288,7 +288,10 @@ def hip_bias_act_(y: torch.Tensor, bias: torch.Tensor, res, act: bool, post=None
 
 
 def maxpool2(x: torch.Tensor) -> torch.Tensor:
-    """2x2/2 max pool; HIP kernel on channels-last fp16, torch elsewhere."""
+    """2x2/2 max pool; HIP kernel on channels-last fp16, torch elsewhere.
+    The HIP pools (pp_maxpool2_f16 and the pooled output of pp_pw_pool_f16 / pp_pw_cat_f16, bit for bit alike) return the maximum of a
+    window's non-NaN elements: NaN only when all four are NaN, and +0 for a window of mixed-sign zeros (include/posepaf.h).  The torch
+    fallback (odd sizes, host tensors, other types) propagates NaN instead: a window with one NaN gives NaN there."""
     n, c, h, w = x.shape
     if not (x.is_cuda and x.dtype == torch.float16 and c % 8 == 0 and h % 2 == 0 and w % 2 == 0):
         _fallback("maxpool2", x, "needs fp16, channels % 8 == 0, even height and width")

@@ -174,7 +174,10 @@ PP_API int pp_time_map_prepass(pp_ctx *ctx, int batch, const void *net_out_dev, 
  * channels % 8 == 0 and 16-byte aligned pointers:
  *   pp_bias_act_f16 : in place  y = act(y + bias[c] (+ residual)) (+ post),  act = LeakyReLU(slope) if has_act;
  *                     n_elems = N*H*W*C; bias fp16[channels]; residual / post may be NULL
- *   pp_maxpool2_f16 : y[n][ho][wo][c] = max of the 2x2 window of x (x is (n, 2*h_out, 2*w_out, c))
+ *   pp_maxpool2_f16 : y[n][ho][wo][c] = max of the 2x2 window of x (x is (n, 2*h_out, 2*w_out, c)): the maximum of the window's
+ *                     non-NaN elements (IEEE 754-2019 maximumNumber), so NaN only when all four are NaN, and +0 for a window that
+ *                     holds +0 and -0 and nothing larger.  The pooled output of pp_pw_pool_f16 / pp_pw_cat_f16 follows the same rule
+ *                     bit for bit: the tuner may take either kernel for one layer.  (torch's max_pool2d propagates NaN instead.)
  *   pp_upsample2_f16: nearest x2: y (n, 2*h_in, 2*w_in, c) from x (n, h_in, w_in, c) */
 PP_API int pp_bias_act_f16(void *y, const void *bias, const void *residual, const void *post, long n_elems, int channels,
                            float slope, int has_act, void *stream);
@@ -314,7 +317,9 @@ PP_API int pp_pw_pre_f16(const void *x, const void *scale, const void *pre_add, 
                          int c_in, int c_out, int ldy, float slope, void *stream);
 /* The same with the 2x2 / stride-2 max-pool of the tensor it produces (y; y2 in mode 4) as one more output -- the hourglass pools
  * exactly these tensors (`low = hg[i][1](pool(x))`, models/layers_transposed.py:262-266), so its pooling passes disappear.
- * pool_out: DEVICE (n, h / 2, w / 2, c_out); width = w: a multiple of 32 (64 when c_in = 64); h even.  y may be NULL: the
+ * pool_out: DEVICE (n, h / 2, w / 2, c_out); width = w: a multiple of 32 (64 when c_in = 64); h even.  The pooled value is
+ * pp_maxpool2_f16's, bit for bit: the maximum of the window's non-NaN elements, NaN only when all four are NaN, +0 above -0
+ * (tests/test_gpu_helper_kernels.py runs both on one tensor).  y may be NULL: the
  * full-resolution tensor is then not written (a caller that reads only the pooled one); y = NULL without pool_out is
  * PP_ERR_BAD_ARG. */
 PP_API int pp_pw_pool_f16(const void *x, const void *scale, const void *w, const void *bias, const void *extra, const void *extra2,

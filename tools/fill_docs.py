@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Substitute the @PLACEHOLDER@ numbers of DESIGN.md / README.md from the bench lines kept under profiles/ (round 3) and the
-tables of DESIGN section 6, round 27, from the probes' JSON (numbers only: the prose lives in the templates).
+tables of DESIGN section 6, rounds 27 and 28, from the probes' JSON (numbers only: the prose lives in the templates).
 Idempotent: the templates live in DESIGN.md.in / README.md.in next to the outputs."""
 import json
 import os
@@ -53,7 +53,20 @@ def round27():
             "R27ACC": f"{4 * (dg + wg):.1f}", "R27PARENT": "\n".join(prows), "R27PROCESSES": "\n".join(procs)}
 
 
+def round28():
+    """the tables of DESIGN section 6, round 28, from profiles/r28_helper_tests.json (the pytest logs of the built library and of each
+    mutated one, tests/test_gpu_helper_kernels.py with the two older helper tests of tests/test_gpu_model.py)"""
+    doc = json.load(open(os.path.join(ROOT, "profiles", "r28_helper_tests.json")))
+    names = lambda d: ", ".join(f"`{k}` ({v})" for k, v in d.items()) or "—"
+    rows = [f"| {m['edit']} | {names(m['old_tests_failed'])} | {names(m['new_tests_failed'])} |" for m in doc["mutants"].values()]
+    real = doc["real"]
+    bounds = "\n".join(f"| {k} | {v:.4f} |" for k, v in real["err_over_bound"].items())
+    return {"R28MUT": "\n".join(rows), "R28BOUND": bounds, "R28WALL": f"{real['wall_s']:.1f}", "R28PASSED": str(real["passed"]),
+            "R28SLOWEST": f"{float(real['slowest'][0][0]):.1f}"}
+
+
 vals.update(round27())
+vals.update(round28())
 for name in ("DESIGN.md", "README.md"):
     src = os.path.join(ROOT, name + ".in")
     if not os.path.exists(src):
